@@ -792,6 +792,33 @@ def cfg5_easgd_block(aslp, dev, native_parallel, comm, rank, world, sync_period)
     return out
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_PARAM_SAMPLE = 4 << 20   # of cfg2's 23.8 M parameters (95 MB in full)
+
+
+def dump_outputs(out_dir, net, xent):
+    """--dump-outputs: what the caller of the timed step (Nnet.TrainStepXent) holds after its last timed step, one float32 / float64 .npy
+    per array: the activations the loss read (the last AffineTransform's output: the step leaves the final Softmax to the loss kernel, so
+    posteriors are never stored), the diff that came back to that layer from the loss (posteriors - targets), the updated parameters (a
+    fixed seeded sample, the same indices in every run and every build) and the loss accumulators.  The net's initialisation, the minibatch and the
+    number of steps in front of this point all follow from the command line, so two builds run with the same arguments are comparable
+    array for array."""
+    import numpy as np
+    params = net.GetParams()
+    pick = np.random.default_rng(4242).integers(0, params.size, min(params.size, DUMP_PARAM_SAMPLE))
+    st = xent.GetStats()
+    last_affine = max(c for c in range(net.NumComponents()) if "AffineTransform" in net.Marker(c))
+    arrays = {"logits": net.ComponentOutput(last_affine, MB, OUT_DIM),
+              "output_diff": net.ComponentOutDiff(last_affine, MB, OUT_DIM),
+              "params_sample": params[pick],
+              "xent_stats": np.array([st[k] for k in ("frames", "correct", "loss", "entropy", "likelyhood")], np.float64)}
+    assert sum(a.nbytes for a in arrays.values()) <= DUMP_LIMIT_BYTES
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def launch_ranks(args):
     """`python bench.py --gpus N` from a bare shell (no launcher environment): start N ranks, one process per GPU, and hand
     back rank 0's JSON line.  This parent never touches the GPU (no torch.cuda call, no HIP call): the children are ordinary
@@ -875,6 +902,7 @@ def main():
                     help="only the cfg2 step itself (profiler passes: nothing but the timed workload's kernels in the trace); implies the --no-* flags")
     ap.add_argument("--no-e2e-tool", action="store_true", help="skip the end-to-end command-line block of the JSON line (extra key e2e_tool)")
     ap.add_argument("--e2e-frames", type=int, default=1024000)
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps write what the last of them computed to DIR/<name>.npy (rank 0; see dump_outputs)")
     ap.add_argument("--dry-run-ranks", action="store_true", help=argparse.SUPPRESS)   # launcher plumbing test (no GPU): tests/test_bench_cpu.py
     args = ap.parse_args()
     if args.headline_only:
@@ -998,6 +1026,8 @@ def main():
     elapsed = time.perf_counter() - t0
     if comm is not None:
         elapsed = comm.MaxOverRanks(elapsed)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, net, xent)   # here: the steps below train the same net further
     # Five more windows of the same K steps (N = 1): `value` above is the driver-comparable one; the spread of short windows on this box
     # -- minimum, median, maximum -- goes into the line beside it (extra key `windows`)
     windows = []

@@ -108,3 +108,35 @@ def test_single_gpu_line_quotes_every_fraction_against_the_instruction_it_issued
         assert str(cb["cores"]) in cb["thread_probe_frames_per_sec"] and "thread_choice" in cb
     assert cb1["value"] > 0 and "WITHOUT BatchNormalization" in cb1["sample"]
     assert c1["vs_cfg1_cpu_baseline"] == pytest.approx(c1["frames_per_sec"] / cb1["value"], rel=1e-6) and c1["vs_cfg1_cpu_baseline"] > 30.0
+
+
+def test_dump_outputs_holds_the_last_timed_step_and_repeats_from_run_to_run(tmp_path):
+    """`--dump-outputs DIR`: the arrays the caller of the timed step holds after its last timed step, as float32 / float64 .npy files of at most
+    64 MB together; `--steps K` is the number of timed steps (the loss accumulators in the dump have seen W + K minibatches, nothing else, when
+    no pre-warm is asked for); the same command line gives the same inputs, so a second run reproduces the arrays."""
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in CLEAN}
+
+    def run(d):
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "7", "--warmup", "2", "--prewarm-steps", "0", "--headline-only",
+                            "--dump-outputs", str(d)], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
+        assert p.returncode == 0, p.stderr.decode()[-3000:]
+        line = json.loads([l for l in p.stdout.decode().splitlines() if l.startswith("{")][-1])
+        assert line["steps"] == 7 and line["prewarm_steps"] == 0 and line["value"] > 0
+        assert all(f.endswith(".npy") for f in os.listdir(d))
+        return {f[:-4]: np.load(os.path.join(d, f)) for f in os.listdir(d)}
+
+    a, b = run(tmp_path / "a"), run(tmp_path / "b")
+    assert set(a) == set(b) == {"logits", "output_diff", "params_sample", "xent_stats"}
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values()) and sum(v.nbytes for v in a.values()) <= 64 << 20
+    assert a["xent_stats"][0] == (2 + 7) * 1024
+    # one step's forward and backward halves: softmax(logits) - diff is the one-hot target of every frame
+    z = a["logits"].astype(np.float64)
+    assert z.shape == a["output_diff"].shape == (1024, 3000)
+    post = np.exp(z - z.max(axis=1, keepdims=True))
+    post /= post.sum(axis=1, keepdims=True)
+    tgt = np.sort(post - a["output_diff"], axis=1)
+    assert np.abs(tgt[:, -1] - 1.0).max() < 1e-5 and np.abs(tgt[:, :-1]).max() < 1e-5
+    assert np.isfinite(a["params_sample"]).all() and a["params_sample"].std() > 0.0
+    for k in a:
+        np.testing.assert_allclose(a[k], b[k], rtol=1e-4, atol=1e-6, err_msg=k)
