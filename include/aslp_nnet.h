@@ -49,6 +49,16 @@ int aslp_nnet_backpropagate(aslp_nnet_t n, const float *out_diff, int rows, int 
 int aslp_nnet_reset_lstm_streams(aslp_nnet_t n, const int32_t *flags_host, int num_streams);   /* :473 */
 int aslp_nnet_set_seq_lengths(aslp_nnet_t n, const int32_t *lengths_host, int num_streams);    /* :498 */
 int aslp_nnet_set_chunk_size(aslp_nnet_t n, int chunk_size);                                   /* :532 */
+/* Which kernels carried the recurrence of the calling thread's latest recurrent component pass (LSTM family, GruStreams): backward == 0
+ * the latest Propagate, != 0 the latest Backpropagate.  Read-only, like aslp_gemm_last_tile: tests assert it so that a case meant for one
+ * path cannot move to another unnoticed.  In a net of several recurrent components it speaks of the one that ran last. */
+enum {
+  ASLP_RECURRENT_NONE = 0,        /* no recurrent pass on this thread yet */
+  ASLP_RECURRENT_PERSISTENT = 1,  /* one launch for all timesteps (csrc/rnn_persistent.hip) */
+  ASLP_RECURRENT_STEP_FUSED = 2,  /* one fused launch per timestep (csrc/rnn_fused.hip, gru_fused.hip) */
+  ASLP_RECURRENT_UNFUSED = 3      /* a product and cell kernels per timestep (csrc/rnn_cells.hip) */
+};
+int aslp_recurrent_last_path(int backward);
 
 /* Nnet::GetParams (:296) -> host buffer of NumParams floats */
 int aslp_nnet_get_params(aslp_nnet_t n, float *host_buf, int buf_len);

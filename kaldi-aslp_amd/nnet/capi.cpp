@@ -10,6 +10,7 @@
 #include "nnet-loss.h"
 #include "nnet-nnet.h"
 #include "nnet-randomizer.h"
+#include "nnet-recurrent.h"
 #include "warp-ctc.h"
 
 using namespace aslp;
@@ -153,6 +154,7 @@ int aslp_nnet_set_seq_lengths(aslp_nnet_t n, const int32_t *lens, int ns) {
   API_BEGIN n->nnet.SetSeqLengths(std::vector<int32>(lens, lens + ns)); API_END
 }
 int aslp_nnet_set_chunk_size(aslp_nnet_t n, int chunk_size) { API_BEGIN n->nnet.SetChunkSize(chunk_size); API_END }
+int aslp_recurrent_last_path(int backward) { return LastRecurrentPath(backward); }
 
 int aslp_nnet_get_params(aslp_nnet_t n, float *host_buf, int buf_len) {
   API_BEGIN

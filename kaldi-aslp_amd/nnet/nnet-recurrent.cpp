@@ -17,7 +17,10 @@ void CheckK() {
 }
 std::pair<BaseFloat *, int> MatParam(CuMatrix &m) { return std::make_pair(m.Data(), m.NumRows() * m.Stride()); }
 std::pair<BaseFloat *, int> VecParam(CuVector &v) { return std::make_pair(v.Data(), v.Dim()); }
+thread_local int t_last_path[2] = {kRecurrentNone, kRecurrentNone};
 }  // namespace
+
+int LastRecurrentPath(int pass) { return t_last_path[pass != 0]; }
 
 // ---- one LSTM direction ---------------------------------------------------------------------------
 void LstmDir::AllocCorr() {
@@ -723,6 +726,7 @@ void LstmFamily::PropagateFnc(const CuMatrixBase &in, CuMatrixBase *out) {
     if (nwin > 1) q.s_count = per_launch;
     const bool persistent = aslp_lstm_seq_supported(&q, 0) != 0;
     last_persistent_ = persistent;
+    t_last_path[0] = persistent ? kRecurrentPersistent : kRecurrentStepFused;
     if (cfg_.bidir) LstmDir::ForwardPreparePair(f_, b_, in, T, S, carried ? &prev_state_ : nullptr, &f_buf_, &b_buf_, persistent, planes_.get());
     else f_.ForwardPrepare(in, T, S, false, carried ? &prev_state_ : nullptr, &f_buf_, persistent);
     // The carried history holds r(0) = m(0) W_rm^T formed with the weights of the PREVIOUS batch (the reference
@@ -783,6 +787,7 @@ void LstmFamily::PropagateFnc(const CuMatrixBase &in, CuMatrixBase *out) {
     if (cfg_.bidir) out_written = LstmDir::ForwardFinishPair(f_, b_, T, S, &f_buf_, &b_buf_, out, planes_.get());
     else out_written = f_.ForwardFinish(T, S, &f_buf_, out, 0);
   } else {
+    t_last_path[0] = kRecurrentUnfused;
     f_.Forward(in, T, S, false, carried ? &prev_state_ : nullptr, nullptr, &f_buf_);
     if (cfg_.bidir) b_.Forward(in, T, S, true, nullptr, cfg_.lc ? nullptr : &seq_len_dev_, &b_buf_);
   }
@@ -820,6 +825,7 @@ void LstmFamily::BackpropagateFnc(const CuMatrixBase &in, const CuMatrixBase &, 
     const int per_launch = 64 / q.ndir, nwin = (S + per_launch - 1) / per_launch;   // stream windows as in PropagateFnc
     if (nwin > 1) q.s_count = per_launch;
     const bool persistent = aslp_lstm_seq_supported(&q, 1) != 0;
+    t_last_path[1] = persistent ? kRecurrentPersistent : kRecurrentStepFused;
     if (cfg_.bidir) LstmDir::BackwardPreparePair(f_, b_, od_f, od_b, T, S, &f_dbuf_, &b_dbuf_, persistent, planes_.get());
     else f_.BackwardPrepare(od_f, T, S, &f_dbuf_, persistent);
     ASLP_ASSERT(f_dbuf_.Stride() == f_buf_.Stride());
@@ -897,6 +903,7 @@ void LstmFamily::BackpropagateFnc(const CuMatrixBase &in, const CuMatrixBase &, 
       f_.BackwardFinish(od_f, T, S, false, &f_dbuf_, in_diff, 0.0, !dr_deferred);
     }
   } else {
+    t_last_path[1] = kRecurrentUnfused;
     f_.Backward(CuSubMatrix(out_diff, 0, T * S, 0, rec), T, S, false, f_buf_, &f_dbuf_, in_diff, 0.0);
     if (cfg_.bidir) b_.Backward(CuSubMatrix(out_diff, 0, T * S, rec, rec), T, S, true, b_buf_, &b_dbuf_, in_diff, 1.0);
   }
@@ -1072,6 +1079,7 @@ void GruStreams::PropagateFnc(const CuMatrixBase &in, CuMatrixBase *out) {  // :
     }
   }
   const bool fused = !persistent && !unfused && aslp_gru_step_supported(H);
+  t_last_path[0] = persistent ? kRecurrentPersistent : fused ? kRecurrentStepFused : kRecurrentUnfused;
   for (int t = 1; t <= T && fused; t++)
     aslp_gru_step_forward(buf_.RowData(t * S), buf_.RowData((t - 1) * S), w_zr_h_.Data(), w_zr_h_.Stride(), w_m_g_.Data(), w_m_g_.Stride(), ld, S, H);
   for (int t = 1; t <= T && !fused && !persistent; t++) {
@@ -1108,6 +1116,7 @@ void GruStreams::BackpropagateFnc(const CuMatrixBase &in, const CuMatrixBase &, 
   const int ld = dbuf_.Stride();
   ASLP_ASSERT(ld == buf_.Stride());
   const bool fused = !persistent && !unfused && aslp_gru_step_supported(H);
+  t_last_path[1] = persistent ? kRecurrentPersistent : fused ? kRecurrentStepFused : kRecurrentUnfused;
   if (fused || persistent) {  // the backward products read W (not W^T): keep K-contiguous transposed copies, refreshed here once per call
     if (w_zr_h_t_.NumRows() != H) { w_zr_h_t_.Resize(H, 2 * H, kUndefined); w_m_g_t_.Resize(H, H, kUndefined); }
     w_zr_h_t_.CopyFromMatTrans(w_zr_h_);

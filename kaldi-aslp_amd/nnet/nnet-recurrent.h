@@ -23,6 +23,16 @@
 
 namespace aslp {
 
+// Which kernels carried the recurrence of the calling thread's latest recurrent PropagateFnc (pass 0) / BackpropagateFnc (pass 1):
+// written where those functions choose (nnet-recurrent.cpp), read by tests through aslp_recurrent_last_path (include/aslp_nnet.h)
+enum RecurrentPath {
+  kRecurrentNone = 0,         // no recurrent pass on this thread yet
+  kRecurrentPersistent = 1,   // one launch for all timesteps (csrc/rnn_persistent.hip)
+  kRecurrentStepFused = 2,    // one fused launch per timestep (csrc/rnn_fused.hip, gru_fused.hip)
+  kRecurrentUnfused = 3       // products and cell kernels per timestep (csrc/rnn_cells.hip)
+};
+int LastRecurrentPath(int pass);
+
 class RecurrentBase : public UpdatableComponent {
  public:
   RecurrentBase(int32 di, int32 dout) : UpdatableComponent(di, dout) {}

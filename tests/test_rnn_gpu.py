@@ -12,6 +12,7 @@ import nnet_io
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-4
+PERSISTENT = 1   # aslp_recurrent_last_path (include/aslp_nnet.h): one launch for all timesteps
 
 # marker: (bidir, proj, cifg, lc, cell_dim_token)
 FAMILY = {
@@ -112,8 +113,9 @@ def test_lstm_family_train_steps_match_oracle(aslp, oracle, dev, tmp_path, marke
 
 @pytest.mark.parametrize("marker", list(FAMILY))
 def test_lstm_family_at_cell_dim_512(aslp, oracle, dev, tmp_path, marker):
-    """Every member of the family at the BASELINE cell size (C = 512, R = 256, S = 32 streams): the fused step kernels' full
-    K-split / tile paths, not the ragged small shapes above.  Two batches, so the carried state and momentum are in play."""
+    """Every member of the family at the BASELINE cell size (C = 512, R = 256, S = 32 streams): the persistent kernels at the largest
+    cell count they take (32 workgroups per chain, all 8 chains), not the ragged small shapes above -- asserted, forward and backward;
+    the per-timestep and unfused kernels have tests/test_rnn_paths_gpu.py.  Two batches, so the carried state and momentum are in play."""
     D, Cc, R, T, S = 64, 512, 256, 12, 32
     bidir, proj, cifg, lc, _ = FAMILY[marker]
     clip, lr, mmt = 5.0, 1e-3, 0.9
@@ -139,9 +141,11 @@ def test_lstm_family_at_cell_dim_512(aslp, oracle, dev, tmp_path, marker):
             net.SetSeqLengths(lens)
         out_ref, idf_ref, state = oracle_step(oracle, marker, dirs, grads, x, od, T, S, state, lens, chunk, lr, mmt, clip)
         out = net.Propagate(torch.from_numpy(x).to(dev)).cpu().numpy()
+        assert aslp.lib.aslp_recurrent_last_path(0) == PERSISTENT, (marker, "forward ran on path", aslp.lib.aslp_recurrent_last_path(0))
         assert oracle.rel_err(out, out_ref) < TOL and oracle.max_err(out, out_ref) < 10 * TOL, ("out", step)
         before = net.GetParams()
         idf = net.Backpropagate(torch.from_numpy(od).to(dev), want_in_diff=True).cpu().numpy()
+        assert aslp.lib.aslp_recurrent_last_path(1) == PERSISTENT, (marker, "backward ran on path", aslp.lib.aslp_recurrent_last_path(1))
         assert oracle.rel_err(idf, idf_ref) < TOL and oracle.max_err(idf, idf_ref) < 10 * TOL, ("in_diff", step)
         after = net.GetParams()
         assert oracle.rel_err(after, flat()) < TOL and oracle.max_err(after, flat()) < 10 * TOL, ("params", step)
