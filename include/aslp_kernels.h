@@ -245,6 +245,16 @@ void aslp_gemm_split16(int on);
  * the choice back to ASLP_GEMM_SPLIT_F16_TILE.  A number the product's layout or epilogue does not admit falls back to the heuristic's
  * choice.  Tests and devtools only: every configuration forms the same bits. */
 void aslp_gemm_split16_tile(int cfg);
+/* Planes those products read per operand.  2 (default): hi and lo, the fp32-equivalent operands above.  1: the hi plane alone -- operands
+ * X16 = fp16(X 2^up) 2^-up with the same per-matrix scale (11 significant bits, no underflow of small gradients), one matrix instruction per
+ * k step, fp32 accumulation and the whole fp32 epilogue: mixed-precision products at half the operand bytes.  Column sums of a transposed A
+ * are then those of A16.  The producers write both planes in either mode, so the mode may change between any two products.  One-plane
+ * products run the 32 x 64 / 64 x 128 / 128 x 128 tiles of gemm_s16_glds and report 404 / 408 / 411 through aslp_gemm_last_tile(); shapes
+ * the split path does not serve, and everything under aslp_gemm_split16(0), stay on the fp32 instruction.  The products inside the recurrent
+ * layers' persistent and per-timestep kernels keep their two pieces.  -1 hands the choice back to ASLP_GEMM_PLANES (1 | 2, default 2,
+ * read once per process).  Process-wide, like aslp_gemm_split16. */
+void aslp_gemm_operand_planes(int n);
+int aslp_gemm_operand_planes_get(void);
 /* Prepared operands of such products: the two fp16 planes of an fp32 matrix, in the matrix' own layout (csrc/split16.h), made once and
  * read by every product the matrix takes part in (as op(A) or op(B), transposed or not).  aslp_planes_convert: one maximum pass and one
  * conversion pass over src [d.rows x d.cols] (cols and stride multiples of 4, 16-byte aligned).  The engine's components keep such

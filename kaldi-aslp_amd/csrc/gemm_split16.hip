@@ -192,7 +192,8 @@ __device__ __forceinline__ float s16_weight_bound(const GemmArgs &g, const S16Vi
 
 // Everything behind the K loop: join the two accumulators and undo the operand scales, the column sums of a reduction-major A
 // (COLSUM), the column statistics, the epilogue (with the planes / maxima of its output when EXTRA).  (row0, col0): this wave's patch.
-template <int TM, int TN, int NW, bool EXTRA, bool COLSUM>
+// NP = 1 (one-plane products): there is no cross-term accumulator to join.
+template <int TM, int TN, int NW, bool EXTRA, bool COLSUM, int NP = 2>
 __device__ __forceinline__ void s16_finish(const GemmArgs &g, const S16View &va, const S16View &vb, f32x16 (&acc)[TM][TN], const f32x16 (&accx)[TM][TN],
                                            const float (&asum)[TM], bool do_colsum, float w_bound, int row0, int col0, int lane, int wave, float *lds) {
   const int l31 = lane & 31, lh = lane >> 5;
@@ -205,7 +206,10 @@ __device__ __forceinline__ void s16_finish(const GemmArgs &g, const S16View &va,
 #pragma unroll
       for (int j = 0; j < TN; j++)
 #pragma unroll
-        for (int q = 0; q < 16; q++) acc[i][j][q] = (fmaf(accx[i][j][q], 0x1p-11f, acc[i][j][q]) * s1) * s2;
+        for (int q = 0; q < 16; q++) {
+          if constexpr (NP == 2) acc[i][j][q] = (fmaf(accx[i][j][q], 0x1p-11f, acc[i][j][q]) * s1) * s2;
+          else acc[i][j][q] = (acc[i][j][q] * s1) * s2;
+        }
   }
   if constexpr (COLSUM) {
     if (do_colsum) {
@@ -282,23 +286,28 @@ __device__ __forceinline__ S16View s16_pick(bool second, const S16View &x, const
 // ABL (devtools/micro/s16_ablate.hip only; 0 in the library): 1 = no MFMA, 2 = no DMA, 4 = no LDS reads -- wrong results, for timing
 // EXTRA: the epilogue also leaves planes / maxima of its output (aslp_gemm_epilogue.planes, *_parts); a variant of its own because the
 // extra epilogue state costs the 128 x 128 tile its last registers.
-template <int BM, int BN, int WGM, int WGN, int NS, bool A_KC, bool B_KC, int ABL = 0, bool EXTRA = false>
+// NP: planes read per operand.  2 = hi and lo (everything above).  1 = the hi plane alone (aslp_gemm_operand_planes(1)): the operands are
+// X16 = fp16(X 2^up) 2^-up, 11 significant bits, a stage is A_hi | B_hi, a k step is ONE matrix instruction into the one accumulator -- half
+// the bytes through L2 -> LDS, half the LDS reads, a third of the matrix instructions; the pipeline, the images and the epilogue are the same.
+template <int BM, int BN, int WGM, int WGN, int NS, bool A_KC, bool B_KC, int ABL = 0, bool EXTRA = false, int NP = 2>
 __global__ void __launch_bounds__(64 * WGM * WGN)
-    __attribute__((amdgpu_waves_per_eu(1, (NS * 2 * (BM + BN) * 128 > 80 * 1024 && WGM * WGN <= 4) ? 1 : 2)))   // (LDS already limits those to one wave per SIMD: all 512 registers are theirs)
+    __attribute__((amdgpu_waves_per_eu(1, (NS * NP * (BM + BN) * 128 > 80 * 1024 && WGM * WGN <= 4) ? 1 : 2)))   // (LDS already limits those to one wave per SIMD: all 512 registers are theirs)
     gemm_s16_glds(GemmArgs g, S16Operands ops) {
   constexpr int NW = WGM * WGN;
   constexpr int WM = BM / WGM, WN = BN / WGN, TM = WM / 32, TN = WN / 32;
   // a stage, in bytes (every plane tile is 64 halves x BR rows whichever way it lies): A_hi | A_lo | B_hi | B_lo
-  constexpr int A_BYTES = BM * 128, B_BYTES = BN * 128, STAGE = 2 * (A_BYTES + B_BYTES);
-  constexpr int SLOTS_A = BM / 8, SLOTS_B = BN / 8, SLOTS = 2 * (SLOTS_A + SLOTS_B);   // 1-KiB DMA units per tile
+  static_assert(NP == 1 || NP == 2, "one or two planes per operand");
+  constexpr int A_BYTES = BM * 128, B_BYTES = BN * 128, STAGE = NP * (A_BYTES + B_BYTES);
+  constexpr int SLOTS_A = BM / 8, SLOTS_B = BN / 8, SLOTS = NP * (SLOTS_A + SLOTS_B);   // 1-KiB DMA units per tile
   static_assert(SLOTS % NW == 0, "DMA units must divide over the waves");
   constexpr int G = SLOTS / NW;
   constexpr int D = NS - 1;
   constexpr int RA = A_KC ? 1 : 2, RB = B_KC ? 1 : 2;            // LDS reads per fragment and plane
-  constexpr int NRH = 2 * (TM * RA + TN * RB);                    // reads per instruction k step
-  constexpr int NM = KH * 3 * TM * TN, NRD = KH * NRH, SB = NM / 2 - 1;
+  constexpr int NRH = NP * (TM * RA + TN * RB);                   // reads per instruction k step
+  constexpr int NI = NP == 2 ? 3 : 1;                             // matrix instructions per k step and pair of fragments
+  constexpr int NM = KH * NI * TM * TN, NRD = KH * NRH, SB = NM / 2 - 1;
   constexpr int UNROLL = (NS % 2 == 0) ? NS : 2 * NS;
-  static_assert(G <= 2 * (SB + 1), "not enough MFMA slots before the barrier");
+  static_assert(G <= (NP == 2 ? 2 : 4) * (SB + 1), "not enough MFMA slots before the barrier");   // (one plane: half the units, a third of the slots)
   static_assert(A_KC || BM == 32 || BM == 64 || BM == 128, "KS image: 32, 64 or 128 columns");
   static_assert(B_KC || BN == 32 || BN == 64 || BN == 128, "KS image: 32, 64 or 128 columns");
   extern __shared__ __attribute__((aligned(1024))) float lds[];
@@ -334,8 +343,8 @@ __global__ void __launch_bounds__(64 * WGM * WGN)
     // the wave count, so WHICH plane unit u of a wave belongs to is a compile-time fact: choosing va / vb members under a run-time
     // condition makes hipcc select between their ADDRESSES, which parks both views in scratch memory (a private segment per launch)
     static_assert(SLOTS_A % NW == 0 && SLOTS_B % NW == 0, "a wave's DMA unit must not straddle planes");
-    constexpr bool is_a = u * NW < 2 * SLOTS_A;
-    constexpr int s2c = is_a ? u * NW : u * NW - 2 * SLOTS_A, per = is_a ? SLOTS_A : SLOTS_B;
+    constexpr bool is_a = u * NW < NP * SLOTS_A;
+    constexpr int s2c = is_a ? u * NW : u * NW - NP * SLOTS_A, per = is_a ? SLOTS_A : SLOTS_B;
     constexpr bool lo_plane = s2c >= per;
     const int sr = (lo_plane ? s2c - per : s2c) + wave;   // unit within the plane tile
     const h16 *base;
@@ -396,10 +405,10 @@ __global__ void __launch_bounds__(64 * WGM * WGN)
     if constexpr (B_KC) {
       const int col = wn * WN + t * 32 + l31;
 #pragma unroll
-      for (int h = 0; h < KH; h++) b_off[t][h] = 2 * A_BYTES + col * 128 + (((2 * h + lh) ^ kc_swizzle(col)) << 4);
+      for (int h = 0; h < KH; h++) b_off[t][h] = NP * A_BYTES + col * 128 + (((2 * h + lh) ^ kc_swizzle(col)) << 4);
     } else {
       const int T = wn * TN + t, krow = 8 * lh + (p16 >> 2);
-      b_off[t][0] = 2 * A_BYTES + krow * (2 * BN) + 64 * (T ^ ks_swizzle<BN>(krow)) + 32 * g16 + 8 * (p16 & 3);
+      b_off[t][0] = NP * A_BYTES + krow * (2 * BN) + 64 * (T ^ ks_swizzle<BN>(krow)) + 32 * g16 + 8 * (p16 & 3);
     }
   }
   struct Frag {
@@ -410,9 +419,9 @@ __global__ void __launch_bounds__(64 * WGM * WGN)
     constexpr int r = decltype(R_)::value, st = decltype(ST_)::value;
     if constexpr (ABL & 4) return;
     constexpr int h = r / NRH, q = r % NRH;
-    constexpr bool is_a = q < 2 * TM * RA;
-    constexpr int q2 = is_a ? q : q - 2 * TM * RA, RR = is_a ? RA : RB;
-    constexpr int t = q2 / (2 * RR), w = q2 % (2 * RR), lo = w / RR, half = w % RR;
+    constexpr bool is_a = q < NP * TM * RA;
+    constexpr int q2 = is_a ? q : q - NP * TM * RA, RR = is_a ? RA : RB;
+    constexpr int t = q2 / (NP * RR), w = q2 % (NP * RR), lo = w / RR, half = w % RR;
     constexpr bool kc = is_a ? A_KC : B_KC;
     constexpr int plane_bytes = is_a ? A_BYTES : B_BYTES, BR = is_a ? BM : BN;
     int base = st * STAGE + (lo ? plane_bytes : 0);
@@ -430,6 +439,8 @@ __global__ void __launch_bounds__(64 * WGM * WGN)
     }
   };
 
+  // (NP == 1: accx and the lo members of Frag are never touched by a matrix instruction or a read and cost no register -- kept so that
+  // the one template serves both plane counts)
   f32x16 acc[TM][TN], accx[TM][TN];   // hi hi; hi lo' + lo' hi
 #pragma unroll
   for (int i = 0; i < TM; i++)
@@ -452,15 +463,18 @@ __global__ void __launch_bounds__(64 * WGM * WGN)
       for (int i = 0; i < TM; i++)
 #pragma unroll
         for (int q = 0; q < 4; q++) {
-          const half2v hv = {f.ah[h][i][2 * q], f.ah[h][i][2 * q + 1]}, lv = {f.al[h][i][2 * q], f.al[h][i][2 * q + 1]};
+          const half2v hv = {f.ah[h][i][2 * q], f.ah[h][i][2 * q + 1]};
           asum[i] = __builtin_amdgcn_fdot2(hv, one, asum[i], false);     // fp32 accumulation of exact fp16 values
-          asum[i] = __builtin_amdgcn_fdot2(lv, eps, asum[i], false);
+          if constexpr (NP == 2) {   // (one plane: the lo fragments are never read -- the sums are those of the operand the product multiplies)
+            const half2v lv = {f.al[h][i][2 * q], f.al[h][i][2 * q + 1]};
+            asum[i] = __builtin_amdgcn_fdot2(lv, eps, asum[i], false);
+          }
         }
   };
   auto mma_unit = [&](const Frag &f, auto M_) {
     constexpr int m = decltype(M_)::value;
     if constexpr (ABL & 1) return;
-    constexpr int n = m % TN, i = (m / TN) % TM, j = (m / (TN * TM)) % 3, h = m / (TN * TM * 3);
+    constexpr int n = m % TN, i = (m / TN) % TM, j = (m / (TN * TM)) % NI, h = m / (TN * TM * NI);
     if constexpr (j == 0) acc[i][n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(f.ah[h][i], f.bh[h][n], acc[i][n], 0, 0, 0);
     else if constexpr (j == 1) accx[i][n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(f.ah[h][i], f.bl[h][n], accx[i][n], 0, 0, 0);
     else accx[i][n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(f.al[h][i], f.bh[h][n], accx[i][n], 0, 0, 0);
@@ -528,7 +542,7 @@ __global__ void __launch_bounds__(64 * WGM * WGN)
   wait_vmcnt<0>();
 
   static_assert(NW * 32 * kEpiPitch * (int)sizeof(float) <= NS * STAGE, "the waves' epilogue slices must fit into the operand LDS");
-  s16_finish<TM, TN, NW, EXTRA, !A_KC>(g, va, vb, acc, accx, asum, do_colsum, w_bound, m0 + wm * WM, n0 + wn * WN, lane, wave, lds);
+  s16_finish<TM, TN, NW, EXTRA, !A_KC, NP>(g, va, vb, acc, accx, asum, do_colsum, w_bound, m0 + wm * WM, n0 + wn * WN, lane, wave, lds);
 }
 
 // ---- both operands reduction-major (the weight gradient dW = dy^T x), 128 x 128 tile ---------------------------------------------
@@ -1026,12 +1040,12 @@ void launch_s16_ks128(GemmArgs &g, const S16Operands &ops) {
   t_last_parts = EXTRA ? g.tiles_m * g.tiles_n * (g.pair ? 2 : 1) : 0;
 }
 
-template <int BM, int BN, int WGM, int WGN, int NS, bool A_KC, bool B_KC, int ABL = 0, bool EXTRA = false>
+template <int BM, int BN, int WGM, int WGN, int NS, bool A_KC, bool B_KC, int ABL = 0, bool EXTRA = false, int NP = 2>
 void launch_s16(GemmArgs &g, const S16Operands &ops) {
   g.tiles_m = (g.M + BM - 1) / BM;
   g.tiles_n = (g.N + BN - 1) / BN;
-  constexpr int lds_bytes = NS * 2 * (BM + BN) * 128;
-  auto kern = gemm_s16_glds<BM, BN, WGM, WGN, NS, A_KC, B_KC, ABL, EXTRA>;
+  constexpr int lds_bytes = NS * NP * (BM + BN) * 128;
+  auto kern = gemm_s16_glds<BM, BN, WGM, WGN, NS, A_KC, B_KC, ABL, EXTRA, NP>;
   static bool attr_set = false;
   if (!attr_set) {
     if (lds_bytes > 48 * 1024)
@@ -1041,12 +1055,44 @@ void launch_s16(GemmArgs &g, const S16Operands &ops) {
   hipLaunchKernelGGL(kern, dim3(g.tiles_m * g.tiles_n, g.split_k > 1 ? g.split_k : 1, g.pair ? 2 : 1), dim3(64 * WGM * WGN), lds_bytes, cur_stream(), g, ops);
   t_last_parts = EXTRA ? g.tiles_m * g.tiles_n * (g.pair ? 2 : 1) : 0;
 }
+// One-plane products (aslp_gemm_operand_planes(1)): the same three tiles of gemm_s16_glds reading the hi planes alone, reported as the
+// two-plane number + 100.  cfg names a tile by either number; the grid-fill reasoning is launch_s16_layout's, with the 128 x 128 threshold measured anew.  gemm_s16_ks128 and gemm_s16_pc
+// have no one-plane form: where two planes would run them, one plane runs 408 / 411.
 template <bool A_KC, bool B_KC>
-bool launch_s16_layout(GemmArgs &g, const S16Operands &ops, int cfg) {
+bool launch_s16_one_plane(GemmArgs &g, const S16Operands &ops, int cfg, bool extra) {
+  if (cfg >= 400) cfg -= 100;
+  if (cfg != 304 && cfg != 308 && !((cfg == 311 || cfg == 312 || cfg == 351) && A_KC && B_KC && !extra)) {
+    const long t128 = (long)((g.M + 127) / 128) * ((g.N + 127) / 128) * (g.pair ? 2 : 1), t64 = (long)((g.M + 63) / 64) * ((g.N + 127) / 128) * (g.pair ? 2 : 1);
+    // 128 x 128 from two full rounds of 256 workgroups on: with one plane the 64 x 128 tile runs two workgroups per CU (72 KB of LDS), so up to
+    // 512 of them are one round -- measured 2048^3 27.0 (408) against 31.9 us (411), 4096 x 2048 x 2048 48.9 against 40.8, 4096^3 173 against
+    // 137 (devtools/bench_gemm_planes.py); grids between 256 and 512 tiles of 128 x 128 were not measured and stay on the 64 x 128 tile
+    cfg = (!extra && A_KC && B_KC && t128 >= 512 && 2 * ((t128 + 255) / 256) <= (t64 + 255) / 256) ? 311 : 308;
+  }
+  switch (cfg) {
+    case 304:
+      if (extra) launch_s16<32, 64, 1, 2, 3, A_KC, B_KC, 0, true, 1>(g, ops);
+      else launch_s16<32, 64, 1, 2, 3, A_KC, B_KC, 0, false, 1>(g, ops);
+      t_last_cfg_s16 = 404;
+      return true;
+    case 308:
+      if (extra) launch_s16<64, 128, 2, 2, 3, A_KC, B_KC, 0, true, 1>(g, ops);
+      else launch_s16<64, 128, 2, 2, 3, A_KC, B_KC, 0, false, 1>(g, ops);
+      t_last_cfg_s16 = 408;
+      return true;
+    default:
+      if constexpr (A_KC && B_KC) launch_s16<128, 128, 2, 2, 2, true, true, 0, false, 1>(g, ops);
+      t_last_cfg_s16 = 411;
+      return true;
+  }
+}
+
+template <bool A_KC, bool B_KC>
+bool launch_s16_layout(GemmArgs &g, const S16Operands &ops, int cfg, int planes) {
   // 128 x 128 where that still gives every CU a workgroup, else 64 x 128 (measured: 1024 x 2048 x 2048 52 against 70 us per call).  Only with
   // both operands reduction-contiguous: the transposing reads' address registers push the 128 x 128 tile past 512 registers (27-31 spilled),
   // and a kernel with a private segment pays ~1 ms per launch for it on this runtime.
   const bool extra = g.ep.planes_of != 0 || g.ep.wmax_parts != nullptr || g.ep.cmax_parts != nullptr || (g.pair && (g.ep1.planes_of != 0 || g.ep1.wmax_parts || g.ep1.cmax_parts));
+  if (planes == 1) return launch_s16_one_plane<A_KC, B_KC>(g, ops, cfg, extra);
   if constexpr (!A_KC && !B_KC) {
     // both operands reduction-major: the 128 x 128 kernel wherever its grid fills the chip about as well as the 64 x 128 one's --
     // rounds of 256 workgroups, a 128 x 128 round costing ~1.6 of a 64 x 128 one (measured on 2048 x 2048 x 1024)
@@ -1100,12 +1146,19 @@ bool launch_s16_layout(GemmArgs &g, const S16Operands &ops, int cfg) {
 
 int g_split16_override = -1;   // aslp_gemm_split16(): -1 = the environment decides
 int g_split16_tile_override = -1;   // aslp_gemm_split16_tile(): -1 = ASLP_GEMM_SPLIT_F16_TILE / the heuristic
+int g_operand_planes_override = -1;   // aslp_gemm_operand_planes(): -1 = ASLP_GEMM_PLANES decides
 
 }  // namespace
 
 bool gemm_split16_enabled() {
   static const bool on = !(getenv("ASLP_GEMM_SPLIT_F16") != nullptr && getenv("ASLP_GEMM_SPLIT_F16")[0] == '0');
   return g_split16_override >= 0 ? g_split16_override != 0 : on;
+}
+
+// planes the products read per operand: 2 (default) or 1 = the hi planes alone (ASLP_GEMM_PLANES, aslp_gemm_operand_planes)
+int gemm_operand_planes() {
+  static const int env = [] { const char *e = getenv("ASLP_GEMM_PLANES"); return e != nullptr && atoi(e) == 1 ? 1 : 2; }();
+  return g_operand_planes_override > 0 ? g_operand_planes_override : env;
 }
 
 int s16_plane_ld(int cols) {
@@ -1271,6 +1324,8 @@ bool gemm_split16_planes_launch(GemmArgs &g, bool a_kc, bool b_kc, const S16View
   auto fits = [&](const S16View &v, bool kc, int outer) { return v.hi && (kc ? (v.rows == outer && v.cols == g.K) : (v.rows == g.K && v.cols == outer)); };
   if (!fits(ops.a, a_kc, g.M) || !fits(ops.b, b_kc, g.N) || !fits(ops.a1, a_kc, g.M) || !fits(ops.b1, b_kc, g.N)) return false;
   t_last_parts = 0;
+  const int planes = gemm_operand_planes();
+  if (planes == 1 && cfg >= 400) cfg -= 100;   // (a one-plane tile asked for by its own number: the choices below speak in two-plane numbers)
   // planes / maxima of the output are written by the 16-byte epilogue only: where that does not apply the request is dropped (the
   // caller sees aslp_gemm_last_parts() == 0 and converts for itself)
   auto drop_extras = [](aslp_gemm_epilogue &ep) { ep.planes_of = 0; ep.wmax_parts = ep.cmax_parts = nullptr; ep.bound_w_parts = ep.bound_c_parts = nullptr; };
@@ -1281,10 +1336,10 @@ bool gemm_split16_planes_launch(GemmArgs &g, bool a_kc, bool b_kc, const S16View
     if (!(g.wide_epilogue && gemm_epilogue_wide_ok(g1))) drop_extras(g.ep1);
   }
   auto launch = [&](GemmArgs &ga, int c) {
-    if (a_kc && b_kc) return launch_s16_layout<true, true>(ga, ops, c);
-    if (a_kc && !b_kc) return launch_s16_layout<true, false>(ga, ops, c);
-    if (!a_kc && !b_kc) return launch_s16_layout<false, false>(ga, ops, c);
-    return launch_s16_layout<false, true>(ga, ops, c);
+    if (a_kc && b_kc) return launch_s16_layout<true, true>(ga, ops, c, planes);
+    if (a_kc && !b_kc) return launch_s16_layout<true, false>(ga, ops, c, planes);
+    if (!a_kc && !b_kc) return launch_s16_layout<false, false>(ga, ops, c, planes);
+    return launch_s16_layout<false, true>(ga, ops, c, planes);
   };
   // A long reduction on a grid that cannot fill the chip (the minibatch-256 layer products: 64 tiles of 64 x 128 for 256 CUs): K is split
   // over blockIdx.y, the chunks' partial products are added in chunk order by gemm_glds.hip's second launch, which also runs the epilogue
@@ -1408,6 +1463,8 @@ void aslp_params_changed(void) {
 }
 void aslp_gemm_split16(int on) { aslp::g_split16_override = on < 0 ? -1 : (on != 0); }
 void aslp_gemm_split16_tile(int cfg) { aslp::g_split16_tile_override = cfg < 0 ? -1 : cfg; }
+void aslp_gemm_operand_planes(int n) { aslp::g_operand_planes_override = (n == 1 || n == 2) ? n : -1; }
+int aslp_gemm_operand_planes_get(void) { return aslp::gemm_operand_planes(); }
 int aslp_gemm_last_parts(void) { return aslp::gemm_split16_last_parts(); }
 void aslp_weight_bound(const float *w_parts, int n_w, const float *c_parts, int n_c, const aslp_planes *a, const aslp_planes *b, int K, float alpha,
                        float beta, float w_alpha, float clip, aslp_planes *w_planes) {

@@ -1,6 +1,7 @@
 """torch.Tensor wrappers over the kernel C ABI (B1/B2).  Tensors must live on the GPU; the
 wrappers only extract (pointer, rows, cols, stride) -- all arithmetic happens in
 libaslp_hip.so.  Used by tests/, bench.py and the Python mirror of the sync workers."""
+import contextlib
 import ctypes as C
 
 import torch
@@ -45,6 +46,25 @@ def sgemm(transA, transB, alpha, A, B, beta, Cm, epilogue=None):
     if rc != 0:
         raise ValueError("aslp_sgemm argument error %d" % rc)
     check_error()
+
+
+def set_operand_planes(n):
+    """planes the layer products read per operand (aslp_gemm_operand_planes): 2 = hi and lo (fp32-equivalent operands), 1 = hi alone
+    (fp16 operands, fp32 accumulation), -1 = what ASLP_GEMM_PLANES said"""
+    lib.aslp_gemm_operand_planes(int(n))
+
+
+@contextlib.contextmanager
+def operand_planes(n):
+    """products inside the block read n planes per operand; the mode in force before comes back on exit (as an explicit setting: where that
+    mode was the environment's, the same value is now pinned -- the environment is read once per process, so nothing changes by it;
+    set_operand_planes(-1) hands the choice back)"""
+    before = lib.aslp_gemm_operand_planes_get()
+    lib.aslp_gemm_operand_planes(int(n))
+    try:
+        yield
+    finally:
+        lib.aslp_gemm_operand_planes(before)
 
 
 class Planes:
