@@ -1,4 +1,4 @@
-// Ablation timings of the split-fp16 product kernel (csrc/gemm_split16.hip): the same launch with the MFMAs, the LDS-DMA or the LDS reads
+// Ablation timings of the split-fp16 product kernel (csrc/gemm_s16_kernels.h gemm_s16_glds, through csrc/gemm_split16.hip and its launchers): the same launch with the MFMAs, the LDS-DMA or the LDS reads
 // taken out (wrong results on purpose), to see which of the three the kernel waits for.
 // Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -I include -I kaldi-aslp_amd/csrc devtools/micro/s16_ablate.hip kaldi-aslp_amd/csrc/runtime.cpp -o devtools/micro/s16_ablate
 #include "../../kaldi-aslp_amd/csrc/gemm_split16.hip"

@@ -1,4 +1,4 @@
-// Producer / consumer split-fp16 product kernels (csrc/gemm_split16.hip gemm_s16_pc) against the one-role kernels they are meant to replace:
+// Producer / consumer split-fp16 product kernels (csrc/gemm_s16_kernels.h gemm_s16_pc, through csrc/gemm_split16.hip and its launchers) against the one-role kernels they are meant to replace:
 // bit-for-bit comparison of the results on random planes, time per launch (interleaved rounds, HIP events), and the ablations (no MFMA /
 // no DMA / no LDS reads) of the new kernels.
 // Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -I include -I kaldi-aslp_amd/csrc devtools/micro/s16_pc.hip kaldi-aslp_amd/csrc/runtime.cpp -o devtools/micro/s16_pc
@@ -94,8 +94,6 @@ int main(int argc, char **argv) {
     run("NT (cfg2 forward)", true, true, 1024, 2048, 2048,
         {V("glds 64x128 4w NS3 (308)", launch_s16<64, 128, 2, 2, 3, true, true>),
          V("pc 64x128 KT64 NS3", launch_s16_pc<64, 128, 64, 3, true, true, false>),
-         VA("pc 64x128 HOT (every request an L2 hit)", launch_s16_pc<64, 128, 64, 3, true, true, false, 0, 4>),
-         VA("pc 64x128 HOT DMA only", launch_s16_pc<64, 128, 64, 3, true, true, false, 5, 4>),
          VA("pc 64x128 no MFMA", launch_s16_pc<64, 128, 64, 3, true, true, false, 1>),
          VA("pc 64x128 no LDS reads (DMA + MFMA)", launch_s16_pc<64, 128, 64, 3, true, true, false, 4>),
          VA("pc 64x128 no DMA", launch_s16_pc<64, 128, 64, 3, true, true, false, 2>),
@@ -106,7 +104,6 @@ int main(int argc, char **argv) {
     run("TN (cfg2 weight gradient)", false, false, 2048, 2048, 1024,
         {V("ks128 128x128 ring4 (328)", launch_s16_ks128<false>),
          V("pc 128x128 KT32 NS4", launch_s16_pc<128, 128, 32, 4, false, false, false>),
-         VA("pc 128x128 NS4 HOT", launch_s16_pc<128, 128, 32, 4, false, false, false, 0, 4>),
          VA("pc 128x128 NS4 no MFMA", launch_s16_pc<128, 128, 32, 4, false, false, false, 1>),
          VA("pc 128x128 NS4 no DMA", launch_s16_pc<128, 128, 32, 4, false, false, false, 2>),
          VA("pc 128x128 NS4 DMA only", launch_s16_pc<128, 128, 32, 4, false, false, false, 5>)});
@@ -114,7 +111,6 @@ int main(int argc, char **argv) {
     run("NT 4096^3", true, true, 4096, 4096, 4096,
         {V("glds 128x128 4w NS2 (311)", launch_s16<128, 128, 2, 2, 2, true, true>),
          V("pc 128x128 KT64 NS2", launch_s16_pc<128, 128, 64, 2, true, true, false>),
-         VA("pc 128x128 NS2 HOT", launch_s16_pc<128, 128, 64, 2, true, true, false, 0, 4>),
          VA("pc 128x128 no MFMA", launch_s16_pc<128, 128, 64, 2, true, true, false, 1>),
          VA("pc 128x128 no DMA", launch_s16_pc<128, 128, 64, 2, true, true, false, 2>)});
   return 0;

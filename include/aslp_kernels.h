@@ -290,6 +290,14 @@ void aslp_gemm_profile_reset(void);
 void aslp_gemm_force_tile(int cfg);
 /* tile configuration of the calling thread's latest aslp_sgemm / aslp_sgemm_ex (the numbers aslp_gemm_profile_tile names) */
 int aslp_gemm_last_tile(void);
+/* What a split-fp16 product of this shape would run on, without launching anything (no device state is touched: callable on a machine
+ * without a GPU): the tile number aslp_gemm_last_tile() reports after the call (csrc/gemm_split16.hip s16_plan: 304 / 308 / 311 / 328 / 351,
+ * one-plane products 404 / 408 / 411), or 0 where the split-fp16 path does not serve the product.  *split_k (may be NULL): the K chunks of
+ * a split reduction, 0 = one launch.  ep / ep1: what the epilogues ask for (NULL: nothing; ep1 != NULL: a pair), taken with a 16-byte
+ * aligned C of leading dimension ldc and the 16-byte epilogue on; planes: 1 or 2, anything else = the mode in force; cfg: a tile asked
+ * for by number (aslp_gemm_split16_tile), 0 = the heuristic. */
+int aslp_gemm_split16_plan(int transA, int transB, int M, int N, int K, int ldc, const aslp_gemm_epilogue *ep, const aslp_gemm_epilogue *ep1,
+                           int planes, int cfg, int *split_k);
 /* variant: 0 = NT, 1 = NN, 2 = TN, 3 = TT.  Returns number of launches. */
 long aslp_gemm_profile_get(int variant, double *flops, double *ms);
 /* the tile configuration that carried most of that variant's flops since the last reset: returns its number, writes a

@@ -155,6 +155,7 @@ _sig("aslp_gemm_profile_reset", None)
 _sig("aslp_gru_seq_supported", _i, C.POINTER(GruSeq), _i)
 _sig("aslp_gemm_force_tile", None, _i)
 _sig("aslp_gemm_last_tile", _i)
+_sig("aslp_gemm_split16_plan", _i, _i, _i, _i, _i, _i, _i, C.POINTER(GemmEpilogue), C.POINTER(GemmEpilogue), _i, _i, C.POINTER(_i))
 _sig("aslp_recurrent_last_path", _i, _i)   # include/aslp_nnet.h: 1 persistent, 2 one fused launch per timestep, 3 unfused
 _sig("aslp_gemm_profile_get", C.c_long, _i, C.POINTER(C.c_double), C.POINTER(C.c_double))
 _sig("aslp_gemm_profile_tile", _i, _i, C.c_char_p, _i)

@@ -311,3 +311,22 @@ def test_producer_consumer_kernel_forms_the_same_bits(aslp, dev, M, N, K):
         C = torch.empty(M, N, device=dev)
         aslp.ops.sgemm(0, 1, 1.0, A, B, 0.0, C)
         assert aslp.lib.aslp_gemm_last_tile() in (351, 308)
+
+
+@pytest.mark.parametrize("tA,tB,M,N,K,cfg", [(0, 1, 1024, 2048, 2048, 0), (0, 1, 2048, 2048, 2048, 0), (1, 0, 2048, 2048, 1024, 0), (0, 0, 256, 2048, 2048, 0),
+                                             (0, 0, 1920, 512, 2048, 0), (0, 1, 1000, 3000, 440, 0), (0, 1, 1024, 2048, 2048, 312), (1, 0, 436, 128, 2052, 308)])
+def test_the_plan_names_the_tile_that_runs(aslp, dev, tA, tB, M, N, K, cfg):
+    """aslp_gemm_split16_plan (the choice as a function that launches nothing, tests/test_gemm_split16_plan_cpu.py) against the tile the real
+    call reports, in both plane modes"""
+    g = torch.Generator(device=dev).manual_seed(M + N + K)
+    A = torch.randn((K, M) if tA else (M, K), device=dev, generator=g)
+    B = torch.randn((N, K) if tB else (K, N), device=dev, generator=g)
+    aslp.lib.aslp_gemm_split16(1)
+    for planes in (2, 1):
+        aslp.lib.aslp_gemm_split16_tile(cfg if cfg else -1)
+        C = torch.zeros(M, N, device=dev)
+        with aslp.ops.operand_planes(planes):
+            aslp.ops.sgemm(tA, tB, 1.0, A, B, 0.0, C)
+            want = aslp.lib.aslp_gemm_split16_plan(tA, tB, M, N, K, N, None, None, 0, cfg, None)
+        assert want != 0 and aslp.lib.aslp_gemm_last_tile() == want, (planes, want, aslp.lib.aslp_gemm_last_tile())
+        assert aslp.lib.aslp_gemm_split16_plan(tA, tB, M, N, K, N, None, None, planes, cfg, None) == want
