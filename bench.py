@@ -11,7 +11,11 @@ with one RCCL all-reduce every `sync_period` frames (default 25600, as the refer
 The layer products run on the fp16 matrix instruction with every fp32 operand carried as two fp16 pieces (csrc/gemm_split16.hip; results
 at least as close to float64 as the fp32 instruction's, `product_accuracy`); `fp32_instruction` is the same step with ASLP_GEMM_SPLIT_F16=0.
 
-Prints ONE JSON line (rank 0).  See DESIGN.md "Measurement" for the roofline / cpu_baseline fields.
+Prints ONE JSON line (rank 0).  A plain run does what the headline needs and nothing else: set-up, warm-up, the timed steps, the
+--dump-outputs arrays, the line.  Everything else the benchmark measures or checks -- the cold-chip figure, further windows, the per-kernel
+pass behind `roofline` / `gemm_all`, cfg1 / cfg3 and the recurrent layers, the fp32 instruction, product accuracy, the bandwidth-bound
+kernels, the CTC check, the command-line tool end to end, the CPU baselines, with N > 1 the cfg4 / cfg3 / cfg5 blocks -- runs under --full.
+See DESIGN.md "Measurement" for the roofline / cpu_baseline fields.
 """
 import argparse
 import ctypes as C
@@ -891,6 +895,9 @@ def main():
     ap.add_argument("--warmup", type=int, default=50)
     ap.add_argument("--prewarm-steps", type=int, default=400, help="untimed steps in front of the warm-up when fewer than 400 steps are timed (clock ramp)")
     ap.add_argument("--sync-period", type=int, default=25600, help="frames between BSP model syncs (N > 1)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything else the line can carry (module docstring); the --no-* flags and --headline-only "
+                         "take parts of it away again")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-gemm-profile", action="store_true", help="do not bracket GEMM launches with HIP events")
     ap.add_argument("--no-update-overlap", action="store_true",
@@ -899,12 +906,15 @@ def main():
     ap.add_argument("--cfg3-bsp-timeout", type=int, default=420, help="N > 1: seconds the extra cfg4_bsp / cfg3_bsp / cfg5_easgd blocks may take before they are dropped")
     ap.add_argument("--launch-timeout", type=int, default=3000, help="N > 1 from a bare shell: seconds the parent waits for rank 0")
     ap.add_argument("--headline-only", action="store_true",
-                    help="only the cfg2 step itself (profiler passes: nothing but the timed workload's kernels in the trace); implies the --no-* flags")
+                    help="with --full: only the cfg2 step itself (cold-chip figure, windows, per-kernel pass); implies --no-cfg3, --no-e2e-tool "
+                         "and --no-cpu-baseline")
     ap.add_argument("--no-e2e-tool", action="store_true", help="skip the end-to-end command-line block of the JSON line (extra key e2e_tool)")
     ap.add_argument("--e2e-frames", type=int, default=1024000)
     ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps write what the last of them computed to DIR/<name>.npy (rank 0; see dump_outputs)")
     ap.add_argument("--dry-run-ranks", action="store_true", help=argparse.SUPPRESS)   # launcher plumbing test (no GPU): tests/test_bench_cpu.py
     args = ap.parse_args()
+    if not args.full:
+        args.headline_only = args.no_gemm_profile = True
     if args.headline_only:
         args.no_cfg3 = args.no_e2e_tool = args.no_cpu_baseline = True
 
@@ -992,15 +1002,18 @@ def main():
     cold_value = None
     if prewarm > 0 and worker is None:
         # the same W warm-up + K timed steps WITHOUT the pre-warm, first thing on the cold chip (extra key `cold_value`): how much of the
-        # headline depends on the pre-warm is then visible in the line itself.  Its steps count towards the pre-warm.
+        # headline depends on the pre-warm is then visible in the line itself.  Its steps count towards the pre-warm.  A plain run makes
+        # the same steps and does not time them: the net in front of the timed steps is the same net with and without --full.
         for _ in range(args.warmup):
             step()
-        torch.cuda.synchronize()
-        tc = time.perf_counter()
+        if args.full:
+            torch.cuda.synchronize()
+            tc = time.perf_counter()
         for _ in range(args.steps):
             step()
-        torch.cuda.synchronize()
-        cold_value = world * args.steps * MB / (time.perf_counter() - tc)
+        if args.full:
+            torch.cuda.synchronize()
+            cold_value = world * args.steps * MB / (time.perf_counter() - tc)
         prewarm_left = max(0, prewarm - args.warmup - args.steps)
     else:
         prewarm_left = prewarm
@@ -1031,7 +1044,7 @@ def main():
     # Five more windows of the same K steps (N = 1): `value` above is the driver-comparable one; the spread of short windows on this box
     # -- minimum, median, maximum -- goes into the line beside it (extra key `windows`)
     windows = []
-    if comm is None:
+    if comm is None and args.full:
         for _ in range(5):
             torch.cuda.synchronize()
             tw = time.perf_counter()
@@ -1040,7 +1053,7 @@ def main():
             torch.cuda.synchronize()
             windows.append(world * args.steps * MB / (time.perf_counter() - tw))
 
-    # Per-kernel durations for the roofline: HIP events around every GEMM launch on the launch stream, over the SAME
+    # Per-kernel durations for the roofline (--full): HIP events around every GEMM launch on the launch stream, over the SAME
     # K steps run once more -- two event records per GEMM inside the timed region cost ~7 % of `value` (measured),
     # so `value` above is timed without them and the kernel timings come from this second, identical pass.
     # The weight-gradient GEMMs normally run on a side stream beside the rest of the backward pass; for the per-kernel

@@ -2,7 +2,7 @@
 mkdir -p gpurun_out/r4
 L=gpurun_out/r4/full.log; : > $L
 timeout 3000 python -m pytest tests -x -q -m gpu 2>&1 | tail -25 >> $L
-timeout 600 python bench.py --steps 200 --warmup 50 --no-cfg3 --no-e2e-tool --no-cpu-baseline 2>&1 | grep -v amdgpu.ids | python -c "
+timeout 600 python bench.py --steps 200 --warmup 50 --full --no-cfg3 --no-e2e-tool --no-cpu-baseline 2>&1 | grep -v amdgpu.ids | python -c "
 import sys, json
 for l in sys.stdin:
     l=l.strip()

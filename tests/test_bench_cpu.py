@@ -38,6 +38,15 @@ def test_launcher_environment_is_respected():
     assert p.returncode == 0 and json.loads(p.stdout.decode())["n_gpus"] == 2
 
 
+def test_full_is_an_option_of_every_rank():
+    """`--full` (everything beside the headline) is parsed by the launcher and handed on to the ranks it starts"""
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "ASLP_COMM_FILE", "ASLP_COMM_TOKEN")}
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2", "--full", "--dry-run-ranks"], env=env,
+                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=120)
+    assert p.returncode == 0, p.stderr.decode()
+    assert json.loads(p.stdout.decode().strip().splitlines()[-1])["n_gpus"] == 2
+
+
 def test_eight_ranks_the_drivers_scale_run():
     """N = 8 (the SCALE run's largest): eight children, one line, every child's status collected"""
     p = run(8)

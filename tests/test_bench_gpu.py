@@ -1,7 +1,8 @@
 """bench.py's N > 1 flow end to end on ONE GPU: with ASLP_COMM_TRANSPORT=shm the ranks are separate processes sharing the device
 (parallel/comm.cpp ShmComm), so the launcher / rendezvous / BSP sync / max-over-ranks timing / cfg3_bsp block / exit status that the
 driver's 2-, 4-, 8-GPU runs go through are exercised where only one GPU exists.  Both launch forms: bench.py's own launcher and
-`python -m torch.distributed.run` (the driver's command line)."""
+`python -m torch.distributed.run` (the driver's command line).  The runs that read the extra blocks ask for them with --full; a plain
+run prints the headline alone."""
 import json
 import os
 import subprocess
@@ -40,7 +41,7 @@ def check_line(out, n):
 def test_bench_two_ranks_own_launcher():
     env = {k: v for k, v in os.environ.items() if k not in CLEAN}
     env["ASLP_COMM_TRANSPORT"] = "shm"
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2"], env=env,
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2", "--full"], env=env,
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert p.returncode == 0, "\n".join(l for l in p.stderr.decode().splitlines() if "ResetLstmStreams" not in l)[-4000:]
     check_line(p.stdout.decode(), 2)
@@ -50,19 +51,19 @@ def test_bench_two_ranks_under_torch_distributed_run():
     env = {k: v for k, v in os.environ.items() if k not in CLEAN}
     env["ASLP_COMM_TRANSPORT"] = "shm"
     p = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-                        "--master-port", "29731", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2"], env=env,
+                        "--master-port", "29731", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2", "--full"], env=env,
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert p.returncode == 0, "\n".join(l for l in p.stderr.decode().splitlines() if "ResetLstmStreams" not in l)[-4000:]
     check_line(p.stdout.decode(), 2)
 
 
 def test_bench_three_ranks_server_and_two_workers():
-    """`bench.py --gpus 3` as the driver would start it for N = 3: cfg4's BSP over three ranks, cfg5's EASGD server on rank 0 with TWO
+    """`bench.py --gpus 3 --full` as the driver would start it for N = 3: cfg4's BSP over three ranks, cfg5's EASGD server on rank 0 with TWO
     workers exchanging with it (the smallest run in which worker-server traffic interleaves), all on one GPU over shared memory --
     so the first real SCALE record cannot fail on plumbing."""
     env = {k: v for k, v in os.environ.items() if k not in CLEAN}
     env["ASLP_COMM_TRANSPORT"] = "shm"
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "3", "--steps", "6", "--warmup", "2"], env=env,
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "3", "--steps", "6", "--warmup", "2", "--full"], env=env,
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=1500)
     assert p.returncode == 0, "\n".join(l for l in p.stderr.decode().splitlines() if "ResetLstmStreams" not in l)[-4000:]
     d = check_line(p.stdout.decode(), 3)
@@ -71,16 +72,17 @@ def test_bench_three_ranks_server_and_two_workers():
 
 
 def test_single_gpu_line_quotes_every_fraction_against_the_instruction_it_issued():
-    """`python bench.py` (N = 1, short): every `frac` in the line is algorithmic TFLOP/s over the peak of the instruction the
+    """`python bench.py --full` (N = 1, short): every `frac` in the line is algorithmic TFLOP/s over the peak of the instruction the
     kernels ISSUE (split-fp16 products: 2516 / 3 TF-equivalent), the ratio to the fp32 instruction's peak lives under `ratio_to_fp32_mfma_peak`;
     the headline carries `roofline` (+ the operand-feed block), `cpu_baseline` (thread probe named) and `cfg1_cpu_baseline` with the
     GPU / CPU ratio on the configuration the >= 30x target is stated on."""
     env = {k: v for k, v in os.environ.items() if k not in CLEAN}
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "30", "--warmup", "5", "--prewarm-steps", "50", "--no-e2e-tool"], env=env,
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "30", "--warmup", "5", "--prewarm-steps", "50", "--full", "--no-e2e-tool"], env=env,
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=1500)
     assert p.returncode == 0, p.stderr.decode()[-3000:]
     d = json.loads([l for l in p.stdout.decode().splitlines() if l.startswith("{")][-1])
     peak16 = 2516.0 / 3.0
+    assert d["cold_value"] > 0 and d["windows"]["count"] == 6 and d["windows"]["min"] <= d["value"] <= d["windows"]["max"]
     r = d["roofline"]
     assert r["bound"] == "mfma" and r["peak"] == pytest.approx(peak16) and r["frac"] == pytest.approx(r["achieved"] / peak16, rel=1e-6)
     assert "ratio_to_fp32_mfma_peak" in r and "frac_of_fp32_mfma_peak" not in r
@@ -108,6 +110,26 @@ def test_single_gpu_line_quotes_every_fraction_against_the_instruction_it_issued
         assert str(cb["cores"]) in cb["thread_probe_frames_per_sec"] and "thread_choice" in cb
     assert cb1["value"] > 0 and "WITHOUT BatchNormalization" in cb1["sample"]
     assert c1["vs_cfg1_cpu_baseline"] == pytest.approx(c1["frames_per_sec"] / cb1["value"], rel=1e-6) and c1["vs_cfg1_cpu_baseline"] > 30.0
+
+
+def test_plain_run_prints_the_headline_and_measures_nothing_else():
+    """`python bench.py --gpus 1 --steps K --warmup W` without --full: the line says what the K timed steps measured (same keys, same meaning as
+    under --full) and carries none of the blocks that take runs of their own; the pre-warm of a short run is still made, untimed."""
+    env = {k: v for k, v in os.environ.items() if k not in CLEAN}
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "2"], env=env,
+                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
+    assert p.returncode == 0, p.stderr.decode()[-3000:]
+    lines = [l for l in p.stdout.decode().splitlines() if l.startswith("{")]
+    assert len(lines) == 1, p.stdout.decode()[-2000:]
+    d = json.loads(lines[0])
+    assert d["metric"] == "frames/sec (aslp-nnet-train)" and d["unit"] == "frames/sec" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert d["n_gpus"] == 1 and d["steps"] == 7 and d["warmup"] == 2 and d["prewarm_steps"] == 398
+    assert d["value"] > 0 and d["value"] == pytest.approx(1024 * 1000.0 / d["ms_per_step"], rel=1e-6)
+    assert d["cold_value"] is None
+    moved = {"windows", "gemm_all", "ctc_loss_fp32_rel_err", "cfg3", "recurrent_layers", "cfg1_gpu", "fp32_instruction", "product_accuracy",
+             "hbm_kernels", "e2e_tool", "cpu_baseline", "cpu_baseline_port", "cfg1_cpu_baseline", "cfg4_bsp", "cfg3_bsp", "cfg5_easgd"}
+    assert not moved & set(d), sorted(moved & set(d))
+    assert "kernel" not in d["roofline"] and "feed" not in d["roofline"]     # whole-step flops over the headline's own time: no per-kernel pass
 
 
 def test_dump_outputs_holds_the_last_timed_step_and_repeats_from_run_to_run(tmp_path):
