@@ -507,6 +507,16 @@ void aslp_device_shared(int on);
  * scales (the default: closer to a float64 product than an fp32 fma chain, csrc/rnn_persistent.hip lstm_seq_fwd_h / lstm_seq_bwd_h).  on = 0
  * puts them on the fp32 instruction v_mfma_f32_4x4x1 (lstm_seq_fwd / lstm_seq_bwd), 1 back, -1 hands the choice to ASLP_LSTM_SPLIT_F16. */
 void aslp_lstm_split16(int on);
+/* fp16 pieces per operand inside those kernels.  2 (default): hi and lo', fp32-equivalent operands.  1 (opt-in): the hi piece alone -- the
+ * recurrent product is fp16(m(t-1)) (fp16(W sc) / sc)^T forward and fp16(dG s) / s times the hi piece of the W_eff rows backward, accumulated in
+ * fp32 in a fixed order; everything outside the product stays fp32.  Any other n hands the choice back to ASLP_LSTM_PIECES (read once; "1"
+ * selects one piece).  aslp_lstm_split16(0) / ASLP_LSTM_SPLIT_F16=0 wins: the fp32 instruction has no pieces.  Independent of
+ * aslp_gemm_operand_planes.  The step-0 W_first product, the GRU kernels and the per-timestep path (csrc/rnn_fused.hip) are not affected. */
+void aslp_lstm_operand_pieces(int n);
+int aslp_lstm_operand_pieces_get(void);
+/* What the calling thread's latest aslp_lstm_seq_forward / _backward launched: 0 = the fp32 instruction, 1 / 2 = the fp16 kernels with that many
+ * pieces per operand.  Read-only, like aslp_gemm_last_tile(). */
+int aslp_lstm_seq_last_pieces(void);
 int aslp_lstm_seq_first_product_supported(int k_first);
 int aslp_lstm_seq_first_product_supported_for(int k_first, int C);   /* ... in a layer of C cells (the staging row is 128 floats for C <= 128) */
 /* Streams per chain the launch for these arguments uses: 8 (one 512-thread workgroup per CU).  grad_partial then has

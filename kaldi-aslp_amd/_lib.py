@@ -161,6 +161,9 @@ _sig("aslp_gemm_profile_get", C.c_long, _i, C.POINTER(C.c_double), C.POINTER(C.c
 _sig("aslp_gemm_profile_tile", _i, _i, C.c_char_p, _i)
 _sig("aslp_gemm_profile_dump", None)
 _sig("aslp_lstm_seq_polls", C.c_uint, _i)
+_sig("aslp_lstm_operand_pieces", None, _i)
+_sig("aslp_lstm_operand_pieces_get", _i)
+_sig("aslp_lstm_seq_last_pieces", _i)
 _sig("aslp_lstm_seq_timing", None, _i, C.POINTER(C.c_ulonglong))
 _sig("aslp_region_profile", None, _i)
 _sig("aslp_region_reset", None)

@@ -500,12 +500,19 @@ __global__ void __launch_bounds__(512) lstm_seq_fwd(aslp_lstm_seq a, SeqStatus s
 // 3-5e-8 of sum |m w| against 0.9-2e-7).  Wave w multiplies its own K slice (as collected) for all gate tiles; the two row halves are
 // joined with v_permlane32_swap and the 8 waves' partial sums go through the same LDS reduction as before.
 // Step 0 with a W_first operand keeps the fp32 instructions (once per launch, operands from LDS).  A/B switch: ASLP_LSTM_SPLIT_F16.
-template <bool CIFG, int NCH, bool FAST>
+// NP: fp16 pieces per operand.  2 = hi and lo' (everything above).  1 = the hi pieces alone (aslp_lstm_operand_pieces(1), opt-in): the
+// product is fp16(m) (fp16(w sc) / sc)^T accumulated in fp32 -- one instruction per (chunk, gate tile), no lo' conversion of m(t-1), no
+// w_lo' fragments.  The A fragment then takes row hr & 7, i.e. the tile's rows 8..15 repeat rows 0..7 and lanes 32..63 hold the lower
+// lanes' results once more: the lower lanes store result registers 0 / 2 and the upper ones 1 / 3 exactly where the joined halves of the
+// two-piece path go, without the v_permlane32_swap.  m(t) as published, the gate block and the W_first product are the same fp32 code.
+template <bool CIFG, int NCH, bool FAST, int NP>
 __global__ void __launch_bounds__(512) lstm_seq_fwd_h(aslp_lstm_seq a, SeqStatus st, unsigned *place) {
+  static_assert(NP == 1 || NP == 2, "one or two fp16 pieces per operand");
+  constexpr int AR = NP == 2 ? 16 : 8;   // operand rows kept in LDS per wave
   constexpr int KW = 32 * NCH;   // K values per wave: NCH chunks of the instruction's 32
   constexpr int G = CIFG ? 3 : 4, KMAX = 8 * KW, MP = KMAX + 4, RP = 80;  // RP = 16 mod 32: the epilogue's reads hit 32 distinct banks
   constexpr int AP = KW + 8;     // halves per operand row: 16-byte reads of 16 rows x 4 k-groups then spread over the banks
-  __shared__ __attribute__((aligned(16))) _Float16 a_h[8][16][AP];   // per wave: rows 0..7 = m_hi of stream r, rows 8..15 = m_lo' of stream r - 8, its K slice
+  __shared__ __attribute__((aligned(16))) _Float16 a_h[8][AR][AP];   // per wave: rows 0..7 = m_hi of stream r, rows 8..15 (NP = 2) = m_lo' of stream r - 8, its K slice
   __shared__ __attribute__((aligned(16))) float m_lds[kChainStreams][MP];
   __shared__ __attribute__((aligned(16))) float wf_lds[64][kFirstK + 4];   // this workgroup's 64 rows of W_first (first step only, see w_first)
   __shared__ float red[2][8][kChainStreams][RP];
@@ -574,7 +581,7 @@ __global__ void __launch_bounds__(512) lstm_seq_fwd_h(aslp_lstm_seq a, SeqStatus
           const float x = wv[tile][j][i] * sc;
           const _Float16 xh = (_Float16)x;
           bh[tile][j][i] = xh;
-          bl[tile][j][i] = (_Float16)(x - (float)xh);   // the residual as it is (<= 8 for the column's largest weight; a subnormal one is < 2^-39 of it)
+          if constexpr (NP == 2) bl[tile][j][i] = (_Float16)(x - (float)xh);   // the residual as it is (<= 8 for the column's largest weight; a subnormal one is < 2^-39 of it)
         }
     }
     __syncthreads();   // the scratch is the reduction buffer of the timesteps
@@ -626,7 +633,7 @@ __global__ void __launch_bounds__(512) lstm_seq_fwd_h(aslp_lstm_seq a, SeqStatus
     const int tp0 = D.reverse ? T + 1 : 0;
     if (live) cprev = D.y[((long)tp0 * S + sq) * ld + oc + cq];
   }
-  for (int p = lane; p < 16 * AP / 8; p += 64) reinterpret_cast<u32x4 *>(&a_h[wave][0][0])[p] = u32x4{0u, 0u, 0u, 0u};   // own wave's rows; read back by this wave only
+  for (int p = lane; p < AR * AP / 8; p += 64) reinterpret_cast<u32x4 *>(&a_h[wave][0][0])[p] = u32x4{0u, 0u, 0u, 0u};   // own wave's rows; read back by this wave only
   unsigned polls = 0u;
   for (int step = 0; step < T; step++) {
     const int t = D.reverse ? T - step : 1 + step, tp = D.reverse ? t + 1 : t - 1;
@@ -671,10 +678,10 @@ __global__ void __launch_bounds__(512) lstm_seq_fwd_h(aslp_lstm_seq a, SeqStatus
           for (int i = 0; i < 4; i++) {
             const float x = __uint_as_float(v[i]);
             hi[i] = (_Float16)x;
-            lo[i] = (_Float16)((x - (float)hi[i]) * 2048.f);
+            if constexpr (NP == 2) lo[i] = (_Float16)((x - (float)hi[i]) * 2048.f);
           }
           *reinterpret_cast<half4 *>(&a_h[wave][stv][kl]) = half4{hi[0], hi[1], hi[2], hi[3]};
-          *reinterpret_cast<half4 *>(&a_h[wave][8 + stv][kl]) = half4{lo[0], lo[1], lo[2], lo[3]};
+          if constexpr (NP == 2) *reinterpret_cast<half4 *>(&a_h[wave][8 + stv][kl]) = half4{lo[0], lo[1], lo[2], lo[3]};
         };
         if (h0) put(v0, st0, kq0);
         if (h1) put(v1, st1, kq1);
@@ -698,24 +705,29 @@ __global__ void __launch_bounds__(512) lstm_seq_fwd_h(aslp_lstm_seq a, SeqStatus
             const f32x4 x4 = *reinterpret_cast<const f32x4 *>(&m_lds[stv][kb + kl]);
             _Float16 hi[4], lo[4];
 #pragma unroll
-            for (int i = 0; i < 4; i++) { hi[i] = (_Float16)x4[i]; lo[i] = (_Float16)((x4[i] - (float)hi[i]) * 2048.f); }
+            for (int i = 0; i < 4; i++) {
+              hi[i] = (_Float16)x4[i];
+              if constexpr (NP == 2) lo[i] = (_Float16)((x4[i] - (float)hi[i]) * 2048.f);
+            }
             *reinterpret_cast<half4 *>(&a_h[wave][stv][kl]) = half4{hi[0], hi[1], hi[2], hi[3]};
-            *reinterpret_cast<half4 *>(&a_h[wave][8 + stv][kl]) = half4{lo[0], lo[1], lo[2], lo[3]};
+            if constexpr (NP == 2) *reinterpret_cast<half4 *>(&a_h[wave][8 + stv][kl]) = half4{lo[0], lo[1], lo[2], lo[3]};
           }
         }
         __builtin_amdgcn_wave_barrier();
       }
       half8 af[NCH];
 #pragma unroll
-      for (int j = 0; j < NCH; j++) af[j] = *reinterpret_cast<const half8 *>(&a_h[wave][hr][32 * j + 8 * hg]);
+      for (int j = 0; j < NCH; j++) af[j] = *reinterpret_cast<const half8 *>(&a_h[wave][NP == 2 ? hr : hr & 7][32 * j + 8 * hg]);
 #pragma unroll
       for (int tile = 0; tile < 4; tile++) hacc[tile] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int j = 0; j < NCH; j++) {
 #pragma unroll
         for (int tile = 0; tile < G; tile++) hacc[tile] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[j], bh[tile][j], hacc[tile], 0, 0, 0);
+        if constexpr (NP == 2) {
 #pragma unroll
-        for (int tile = 0; tile < G; tile++) hacc[tile] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[j], bl[tile][j], hacc[tile], 0, 0, 0);
+          for (int tile = 0; tile < G; tile++) hacc[tile] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[j], bl[tile][j], hacc[tile], 0, 0, 0);
+        }
       }
     }
     if (first_special) {   // r(0) W_first^T, both operands from LDS; this wave's slice of K = k_first
@@ -740,11 +752,18 @@ __global__ void __launch_bounds__(512) lstm_seq_fwd_h(aslp_lstm_seq a, SeqStatus
       const int hg2 = hg & 1, eodd = lane >> 5;
 #pragma unroll
       for (int tile = 0; tile < G; tile++) {
-        const float f = lane < 32 ? inv_sc[tile] : inv_sc[tile] * 0x1p-11f;
+        if constexpr (NP == 2) {
+          const float f = lane < 32 ? inv_sc[tile] : inv_sc[tile] * 0x1p-11f;
 #pragma unroll
-        for (int e = 0; e < 4; e += 2) {
-          const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(hacc[tile][e] * f), __float_as_uint(hacc[tile][e + 1] * f), false, false);
-          red[par][wave][4 * hg2 + e + eodd][16 * tile + hr] = __uint_as_float(sw[0]) + __uint_as_float(sw[1]);   // stream = result row 4 (l >> 4 & 1) + e (+ 1 in the upper lanes)
+          for (int e = 0; e < 4; e += 2) {
+            const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(hacc[tile][e] * f), __float_as_uint(hacc[tile][e + 1] * f), false, false);
+            red[par][wave][4 * hg2 + e + eodd][16 * tile + hr] = __uint_as_float(sw[0]) + __uint_as_float(sw[1]);   // stream = result row 4 (l >> 4 & 1) + e (+ 1 in the upper lanes)
+          }
+        } else {
+          // one piece: both lane halves hold fp16(m) w_hi of the same streams (rows 8..15 repeat rows 0..7); the same store pattern, no join
+#pragma unroll
+          for (int e = 0; e < 4; e += 2)
+            red[par][wave][4 * hg2 + e + eodd][16 * tile + hr] = (eodd ? hacc[tile][e + 1] : hacc[tile][e]) * inv_sc[tile];
         }
       }
     } else {
@@ -1055,11 +1074,15 @@ __global__ void __launch_bounds__(512) lstm_seq_bwd(aslp_lstm_seq a, SeqStatus s
 // longest phase of a backward timestep (1.4 of ~3 us).  The gate diffs a workgroup multiplies are its own (LDS), so their power-of-two
 // scale is per stream AND timestep (the largest of the 16 * G values of a stream goes to [2^13, 2^14)): gradients of any magnitude keep 22
 // significant bits.  The share layout inside a producer -> consumer block changes with the instruction's result layout (8-byte pieces).
-template <bool CIFG, int TPW>
+// NP = 1 (aslp_lstm_operand_pieces(1)): fp16(dG s) and the hi piece of the W_eff rows alone, as in lstm_seq_fwd_h -- rows 8..15 of the A tile
+// repeat rows 0..7, so every lane still sends ONE 8-byte piece to the same inbox offset (registers 0 / 2 from the lower lanes, 1 / 3 from the
+// upper) and the consumer side, the ring and dmax_parts are what they are with two pieces.
+template <bool CIFG, int TPW, int NP>
 __global__ void __launch_bounds__(512) lstm_seq_bwd_h(aslp_lstm_seq a, SeqStatus st, unsigned *place, float *inbox) {
-  constexpr int G = CIFG ? 3 : 4;
+  static_assert(NP == 1 || NP == 2, "one or two fp16 pieces per operand");
+  constexpr int G = CIFG ? 3 : 4, AR = NP == 2 ? 16 : 8;
   constexpr int AP = 64 + 8;   // halves per operand row: K = the workgroup's own 16 * G gate columns (two chunks of 32; CIFG leaves 16 zeros)
-  __shared__ __attribute__((aligned(16))) _Float16 a_h[2][16][AP];        // [parity][rows 0..7 = dG_hi of stream r, 8..15 = dG_lo' of stream r - 8][gate * 16 + cell]
+  __shared__ __attribute__((aligned(16))) _Float16 a_h[2][AR][AP];        // [parity][rows 0..7 = dG_hi of stream r, 8..15 (NP = 2) = dG_lo' of stream r - 8][gate * 16 + cell]
   __shared__ __attribute__((aligned(16))) float row_inv[2][kChainStreams];   // [parity][stream]: 1 / (the power of two its gate diffs were scaled by)
   __shared__ __attribute__((aligned(16))) float dmsum[128];   // the chain's shares of this workgroup's 8 x 16 d_m values, summed (layout of one producer block)
   __shared__ float shares[kChainStreams * 7 * 16];              // scratch of the final bias / peephole reduction
@@ -1119,10 +1142,10 @@ __global__ void __launch_bounds__(512) lstm_seq_bwd_h(aslp_lstm_seq a, SeqStatus
         const float x = wv[j][i] * sc;
         const _Float16 xh = (_Float16)x;
         bh[tj][j][i] = xh;
-        bl[tj][j][i] = (_Float16)(x - (float)xh);
+        if constexpr (NP == 2) bl[tj][j][i] = (_Float16)(x - (float)xh);
       }
   }
-  for (int p = threadIdx.x; p < 2 * 16 * AP / 8; p += 512) reinterpret_cast<u32x4 *>(&a_h[0][0][0])[p] = u32x4{0u, 0u, 0u, 0u};   // (the loop's first barrier publishes it)
+  for (int p = threadIdx.x; p < 2 * AR * AP / 8; p += 512) reinterpret_cast<u32x4 *>(&a_h[0][0][0])[p] = u32x4{0u, 0u, 0u, 0u};   // (the loop's first barrier publishes it)
   // inbox geometry
   const size_t slot_words = (size_t)kMaxChains * kMaxWgPerChain * kMaxWgPerChain * 128;  // floats per ring slot
   float *chain_box = inbox + (size_t)chain * kMaxWgPerChain * kMaxWgPerChain * 128;
@@ -1159,7 +1182,7 @@ __global__ void __launch_bounds__(512) lstm_seq_bwd_h(aslp_lstm_seq a, SeqStatus
       {
         half8 af[2];
 #pragma unroll
-        for (int j = 0; j < 2; j++) af[j] = *reinterpret_cast<const half8 *>(&a_h[par ^ 1][hr][32 * j + 8 * hg]);
+        for (int j = 0; j < 2; j++) af[j] = *reinterpret_cast<const half8 *>(&a_h[par ^ 1][NP == 2 ? hr : hr & 7][32 * j + 8 * hg]);
         const f32x4 rinv = *reinterpret_cast<const f32x4 *>(&row_inv[par ^ 1][4 * hg2]);   // streams 4 hg2 + e of this lane's result registers
         f32x4 hacc[TPW];
 #pragma unroll
@@ -1168,8 +1191,10 @@ __global__ void __launch_bounds__(512) lstm_seq_bwd_h(aslp_lstm_seq a, SeqStatus
         for (int j = 0; j < 2; j++) {
 #pragma unroll
           for (int tj = 0; tj < TPW; tj++) hacc[tj] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[j], bh[tj][j], hacc[tj], 0, 0, 0);
+          if constexpr (NP == 2) {
 #pragma unroll
-          for (int tj = 0; tj < TPW; tj++) hacc[tj] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[j], bl[tj][j], hacc[tj], 0, 0, 0);
+            for (int tj = 0; tj < TPW; tj++) hacc[tj] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[j], bl[tj][j], hacc[tj], 0, 0, 0);
+          }
         }
         // 2. hand the shares out.  Rows 0..7 (lanes 0..31) hold dG_hi W, rows 8..15 dG_lo' W of the same streams; one v_permlane32_swap joins
         // the halves of two result registers (see lstm_seq_fwd_h), leaving registers 0 / 2 in the lower lanes and 1 / 3 in the upper: an
@@ -1179,12 +1204,21 @@ __global__ void __launch_bounds__(512) lstm_seq_bwd_h(aslp_lstm_seq a, SeqStatus
 #pragma unroll
         for (int tj = 0; tj < TPW; tj++) {
           const int cb = wave + 8 * tj;
-          const float f = csc[tj] * half_f;
-          const auto s01 = __builtin_amdgcn_permlane32_swap(__float_as_uint(hacc[tj][0] * (f * rinv[0])), __float_as_uint(hacc[tj][1] * (f * rinv[1])), false, false);
-          const auto s23 = __builtin_amdgcn_permlane32_swap(__float_as_uint(hacc[tj][2] * (f * rinv[2])), __float_as_uint(hacc[tj][3] * (f * rinv[3])), false, false);
-          if (cb < wpc) {
-            const float v01 = __uint_as_float(s01[0]) + __uint_as_float(s01[1]), v23 = __uint_as_float(s23[0]) + __uint_as_float(s23[1]);
-            const int off = ((cb * kMaxWgPerChain + me) * 128 + ((hg2 * 2 + eodd) * 16 + hr) * 2) * 4;
+          if constexpr (NP == 2) {
+            const float f = csc[tj] * half_f;
+            const auto s01 = __builtin_amdgcn_permlane32_swap(__float_as_uint(hacc[tj][0] * (f * rinv[0])), __float_as_uint(hacc[tj][1] * (f * rinv[1])), false, false);
+            const auto s23 = __builtin_amdgcn_permlane32_swap(__float_as_uint(hacc[tj][2] * (f * rinv[2])), __float_as_uint(hacc[tj][3] * (f * rinv[3])), false, false);
+            if (cb < wpc) {
+              const float v01 = __uint_as_float(s01[0]) + __uint_as_float(s01[1]), v23 = __uint_as_float(s23[0]) + __uint_as_float(s23[1]);
+              const int off = ((cb * kMaxWgPerChain + me) * 128 + ((hg2 * 2 + eodd) * 16 + hr) * 2) * 4;
+              const u32x2 pk = {__float_as_uint(v01), __float_as_uint(v23)};
+              if (R.local) __builtin_amdgcn_raw_buffer_store_b64(pk, rs, off, 0, 0);
+              else __builtin_amdgcn_raw_buffer_store_b64(pk, rs, off, 0, kAuxSc1);
+            }
+          } else if (cb < wpc) {   // both lane halves hold the same streams' results: the piece this lane holds behind the join, picked directly
+            const float v01 = eodd ? hacc[tj][1] * (csc[tj] * rinv[1]) : hacc[tj][0] * (csc[tj] * rinv[0]);
+            const float v23 = eodd ? hacc[tj][3] * (csc[tj] * rinv[3]) : hacc[tj][2] * (csc[tj] * rinv[2]);
+            const int off = ((cb * kMaxWgPerChain + me) * 128 + ((hg2 * 2 + eodd) * 16 + hr) * 2) * 4;   // the same offset as with two pieces
             const u32x2 pk = {__float_as_uint(v01), __float_as_uint(v23)};
             if (R.local) __builtin_amdgcn_raw_buffer_store_b64(pk, rs, off, 0, 0);
             else __builtin_amdgcn_raw_buffer_store_b64(pk, rs, off, 0, kAuxSc1);
@@ -1277,7 +1311,7 @@ __global__ void __launch_bounds__(512) lstm_seq_bwd_h(aslp_lstm_seq a, SeqStatus
           const float xs = x * sc;
           const _Float16 xh = (_Float16)xs;
           a_h[par][sl][k] = xh;
-          a_h[par][8 + sl][k] = (_Float16)((xs - (float)xh) * 2048.f);
+          if constexpr (NP == 2) a_h[par][8 + sl][k] = (_Float16)((xs - (float)xh) * 2048.f);
         };
         put(cc, dg);
         if (!CIFG) { put(16 + cc, di); put(32 + cc, df); put(48 + cc, dov); }
@@ -1812,21 +1846,32 @@ bool split_f16_on() {   // default on; ASLP_LSTM_SPLIT_F16=0 puts the recurrent 
   static const bool off = getenv("ASLP_LSTM_SPLIT_F16") != nullptr && getenv("ASLP_LSTM_SPLIT_F16")[0] == '0';
   return g_lstm_split_override >= 0 ? g_lstm_split_override != 0 : !off;
 }
-SeqKernel pick_fwd_h(bool cifg, int C) {
+// fp16 pieces per operand inside lstm_seq_fwd_h / lstm_seq_bwd_h: 2 (default), or 1 = the hi pieces alone (ASLP_LSTM_PIECES=1,
+// aslp_lstm_operand_pieces(1)).  Independent of ASLP_GEMM_PLANES; without the fp16 kernels (split_f16_on() false) it has no effect.
+int g_lstm_pieces_override = -1;   // aslp_lstm_operand_pieces(): -1 = the environment decides
+int lstm_pieces() {
+  static const int env = (getenv("ASLP_LSTM_PIECES") != nullptr && getenv("ASLP_LSTM_PIECES")[0] == '1' && getenv("ASLP_LSTM_PIECES")[1] == 0) ? 1 : 2;
+  return g_lstm_pieces_override > 0 ? g_lstm_pieces_override : env;
+}
+template <int NP>
+SeqKernel pick_fwd_h_np(bool cifg, int C) {
   if (fast_act()) {
-    if (C <= 256) return cifg ? lstm_seq_fwd_h<true, 1, true> : lstm_seq_fwd_h<false, 1, true>;
-    if (C <= 512) return cifg ? lstm_seq_fwd_h<true, 2, true> : lstm_seq_fwd_h<false, 2, true>;
+    if (C <= 256) return cifg ? lstm_seq_fwd_h<true, 1, true, NP> : lstm_seq_fwd_h<false, 1, true, NP>;
+    if (C <= 512) return cifg ? lstm_seq_fwd_h<true, 2, true, NP> : lstm_seq_fwd_h<false, 2, true, NP>;
     return nullptr;
   }
-  if (C <= 256) return cifg ? lstm_seq_fwd_h<true, 1, false> : lstm_seq_fwd_h<false, 1, false>;
-  if (C <= 512) return cifg ? lstm_seq_fwd_h<true, 2, false> : lstm_seq_fwd_h<false, 2, false>;
+  if (C <= 256) return cifg ? lstm_seq_fwd_h<true, 1, false, NP> : lstm_seq_fwd_h<false, 1, false, NP>;
+  if (C <= 512) return cifg ? lstm_seq_fwd_h<true, 2, false, NP> : lstm_seq_fwd_h<false, 2, false, NP>;
   return nullptr;
 }
-SeqKernelB pick_bwd_h(bool cifg, int C) {
-  if (C <= 128) return cifg ? lstm_seq_bwd_h<true, 1> : lstm_seq_bwd_h<false, 1>;
-  if (C <= 512) return cifg ? lstm_seq_bwd_h<true, 4> : lstm_seq_bwd_h<false, 4>;
+template <int NP>
+SeqKernelB pick_bwd_h_np(bool cifg, int C) {
+  if (C <= 128) return cifg ? lstm_seq_bwd_h<true, 1, NP> : lstm_seq_bwd_h<false, 1, NP>;
+  if (C <= 512) return cifg ? lstm_seq_bwd_h<true, 4, NP> : lstm_seq_bwd_h<false, 4, NP>;
   return nullptr;
 }
+SeqKernel pick_fwd_h(bool cifg, int C, int np) { return np == 1 ? pick_fwd_h_np<1>(cifg, C) : pick_fwd_h_np<2>(cifg, C); }
+SeqKernelB pick_bwd_h(bool cifg, int C, int np) { return np == 1 ? pick_bwd_h_np<1>(cifg, C) : pick_bwd_h_np<2>(cifg, C); }
 SeqKernelB pick_bwd(bool cifg, int C) {
   if (C <= 128) return cifg ? lstm_seq_bwd<true, 1> : lstm_seq_bwd<false, 1>;
   if (C <= 512) return cifg ? lstm_seq_bwd<true, 4> : lstm_seq_bwd<false, 4>;
@@ -1889,13 +1934,16 @@ int aslp_lstm_seq_supported(const aslp_lstm_seq *a, int backward) {
   const int ns = a->s_count > 0 ? a->s_count : a->S;   // streams of this launch
   const int nsg = (ns + kChainStreams - 1) / kChainStreams, wpc = (a->C + kCellsPerWg - 1) / kCellsPerWg;
   if (a->ndir * nsg > kMaxChains || wpc > kMaxWgPerChain) return 0;   // <= 32 streams per launch (bidirectional) / 64, C <= 512
-  const void *k = backward ? reinterpret_cast<const void *>(split_f16_on() ? pick_bwd_h(a->cifg != 0, a->C) : pick_bwd(a->cifg != 0, a->C))
-                           : reinterpret_cast<const void *>(split_f16_on() ? pick_fwd_h(a->cifg != 0, a->C) : pick_fwd(a->cifg != 0, a->C));
+  const int np = lstm_pieces();   // the kernel probed is the one launch_seq would start now
+  const void *k = backward ? reinterpret_cast<const void *>(split_f16_on() ? pick_bwd_h(a->cifg != 0, a->C, np) : pick_bwd(a->cifg != 0, a->C))
+                           : reinterpret_cast<const void *>(split_f16_on() ? pick_fwd_h(a->cifg != 0, a->C, np) : pick_fwd(a->cifg != 0, a->C));
   return grid_fits(k, 512, (long)kMaxChains * wpc) ? 1 : 0;
 }
 
 void aslp_device_shared(int on) { device_gate().on = on != 0; }
 void aslp_lstm_split16(int on) { g_lstm_split_override = on < 0 ? -1 : (on != 0); }
+void aslp_lstm_operand_pieces(int n) { g_lstm_pieces_override = (n == 1 || n == 2) ? n : -1; }
+int aslp_lstm_operand_pieces_get(void) { return lstm_pieces(); }
 
 int aslp_lstm_seq_first_product_supported(int k_first) { return k_first > 0 && k_first <= kFirstK && (k_first & 3) == 0; }
 // ... for a layer of C cells: the kernels stage r(0) in LDS rows as long as the K range of their instantiation (128 floats for C <= 128, else 512)
@@ -1923,8 +1971,11 @@ void aslp_lstm_seq_fill_pair(float *buf0, float *buf1, int ld, int T, int S, int
 }
 
 thread_local int t_last_dmax = 0;   // aslp_lstm_seq_last_dmax()
+thread_local int t_last_pieces = 0;   // aslp_lstm_seq_last_pieces()
 static void launch_seq(const aslp_lstm_seq *a, bool backward, const char *who) {
   if (backward) t_last_dmax = 0;
+  const bool split = split_f16_on();
+  const int np = lstm_pieces();   // read once: the probe below and the launch see the same kernel
   if (!seq_args_ok(a) || !aslp_lstm_seq_supported(a, backward ? 1 : 0)) {
     set_error(std::string(who) + ": arguments outside what the persistent kernel supports (check aslp_lstm_seq_supported first)");
     return;
@@ -1962,12 +2013,13 @@ static void launch_seq(const aslp_lstm_seq *a, bool backward, const char *who) {
   SeqStatus st = {rt.abort_flag, rt.host_err_dev, ((rt.timing_mode == 1 && !backward) || (rt.timing_mode == 2 && backward)) ? rt.timing : nullptr,
                   ((rt.timing_mode == 3 && !backward) || (rt.timing_mode == 4 && backward)) ? rt.timing + 8 : nullptr, rt.epoch, wave_collect};
   const int wpc = (a->C + kCellsPerWg - 1) / kCellsPerWg;
-  if (!backward) hipLaunchKernelGGL(split_f16_on() ? pick_fwd_h(a->cifg != 0, a->C) : pick_fwd(a->cifg != 0, a->C), dim3(kMaxChains * wpc), dim3(512), 0, cur_stream(), *a, st, rt.place);
+  if (!backward) hipLaunchKernelGGL(split ? pick_fwd_h(a->cifg != 0, a->C, np) : pick_fwd(a->cifg != 0, a->C), dim3(kMaxChains * wpc), dim3(512), 0, cur_stream(), *a, st, rt.place);
   else {
-    hipLaunchKernelGGL(split_f16_on() ? pick_bwd_h(a->cifg != 0, a->C) : pick_bwd(a->cifg != 0, a->C), dim3(kMaxChains * wpc), dim3(512), 0, cur_stream(), *a, st, rt.place, rt.inbox);
+    hipLaunchKernelGGL(split ? pick_bwd_h(a->cifg != 0, a->C, np) : pick_bwd(a->cifg != 0, a->C), dim3(kMaxChains * wpc), dim3(512), 0, cur_stream(), *a, st, rt.place, rt.inbox);
     // (only lstm_seq_bwd_h forms the per-workgroup maxima of the gate diffs, and only a single launch per pass leaves a complete set)
-    if (split_f16_on() && a->s_count == 0 && (a->dmax_parts[0] || a->dmax_parts[1])) t_last_dmax = kMaxChains * wpc;
+    if (split && a->s_count == 0 && (a->dmax_parts[0] || a->dmax_parts[1])) t_last_dmax = kMaxChains * wpc;
   }
+  t_last_pieces = split ? np : 0;
   note_launch(rt);
   check_launch(who);
 }
@@ -2086,5 +2138,6 @@ void aslp_lstm_seq_vec_grads2(const aslp_lstm_seq *a, float *const *vec8_dir0, f
 void aslp_lstm_seq_forward(const aslp_lstm_seq *a) { launch_seq(a, false, "aslp_lstm_seq_forward"); }
 void aslp_lstm_seq_backward(const aslp_lstm_seq *a) { launch_seq(a, true, "aslp_lstm_seq_backward"); }
 int aslp_lstm_seq_last_dmax(void) { return t_last_dmax; }
+int aslp_lstm_seq_last_pieces(void) { return t_last_pieces; }
 
 }  // extern "C"

@@ -67,6 +67,24 @@ def operand_planes(n):
         lib.aslp_gemm_operand_planes(before)
 
 
+def set_lstm_operand_pieces(n):
+    """fp16 pieces per operand inside the persistent LSTM recurrences (aslp_lstm_operand_pieces): 2 = hi and lo' (fp32-equivalent operands),
+    1 = hi alone (fp16 operands, fp32 accumulation), -1 = what ASLP_LSTM_PIECES said"""
+    lib.aslp_lstm_operand_pieces(int(n))
+
+
+@contextlib.contextmanager
+def lstm_operand_pieces(n):
+    """persistent LSTM recurrences inside the block multiply with n pieces per operand; the mode in force before comes back on exit (pinned as
+    an explicit setting, as operand_planes does; set_lstm_operand_pieces(-1) hands the choice back to the environment)"""
+    before = lib.aslp_lstm_operand_pieces_get()
+    lib.aslp_lstm_operand_pieces(int(n))
+    try:
+        yield
+    finally:
+        lib.aslp_lstm_operand_pieces(before)
+
+
 class Planes:
     """the two fp16 planes of an fp32 matrix (aslp_planes_*): made once, read by every product the matrix takes part in"""
 
