@@ -32,6 +32,9 @@
 // the host reports the failure through aslp_get_last_error -- a wrong result is never silent and the GPU never hangs.
 // The grid must be co-resident: aslp_lstm_seq_supported() checks it against the occupancy of the kernel with a margin
 // of one workgroup per CU, otherwise the caller keeps the one-launch-per-timestep path.
+//
+// rnn_seq_parts.h holds what the kernels here share: the file-scope parts (SeqStatus, timers, spin_ok, chain_role, the gate non-linearities ...) and
+// the parts of an LSTM timestep whose extraction left every kernel's instructions as they were; the rest stays in the kernels, with a note at its place.
 #include <fcntl.h>
 #include <sys/file.h>
 #include <unistd.h>
@@ -47,182 +50,11 @@
 #include "common.h"
 #include "scratch.h"
 #include "split16.h"   // SeqFillJob / seq_fill_row: the buffer preparation a conversion launch can take along
+#include "rnn_seq_parts.h"   // the parts the kernels below share
 
 namespace aslp {
 void register_async_error_word(const volatile unsigned *host_word, const char *what);  // runtime.cpp
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-constexpr unsigned kSentinel = 0xFFFFFFFFu;
-constexpr int kAuxSc1 = 16;          // buffer instruction cache policy: sc1 = agent scope
-constexpr long kSpinLimitTicks = 200000000L;  // wall_clock64 runs at 100 MHz: 2 s
-
-__device__ __forceinline__ float dsigm(float y, float d) { return d * y * (1.0f - y); }
-__device__ __forceinline__ float dtanh(float y, float d) { return d * (1.0f - y * y); }
-
-// Every base pointer handed to a buffer instruction here is wave-uniform by construction (kernel arguments, blockIdx, the loop
-// counter), but hipcc cannot always prove it (the direction's pointers are picked from the argument struct with an index that
-// went through shared memory) and then wraps EVERY buffer load / store in a waterfall loop over the lanes' descriptor values.
-// readfirstlane makes the uniformity explicit: the descriptor lives in SGPRs and the access is one instruction.
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const float *p) {
-  const unsigned long long v = reinterpret_cast<unsigned long long>(p);
-  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
-  float *u = reinterpret_cast<float *>(((unsigned long long)hi << 32) | lo);
-  return __builtin_amdgcn_make_buffer_rsrc(u, 0, 0x7fffffff, 0x00020000);
-}
-__device__ __forceinline__ bool has_sentinel(const u32x4 &v) {
-  return v.x == kSentinel || v.y == kSentinel || v.z == kSentinel || v.w == kSentinel;
-}
-__device__ __forceinline__ float as_f(unsigned u) { return __uint_as_float(u); }
-// cross-lane moves on the DPP path of the VALU (no LDS crossbar round trip like ds_bpermute): lane K of the caller's quad, and the
-// lane N places up within the caller's row of 16 lanes
-template <int K>
-__device__ __forceinline__ float quad_bcast(float v) {
-  return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), K * 0x55, 0xF, 0xF, true));   // quad_perm:[K,K,K,K]
-}
-template <int N>
-__device__ __forceinline__ float row_up(float v) {
-  return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x100 + N, 0xF, 0xF, true));  // row_shl:N -> dst[i] = src[i + N]
-}
-
-template <int N>
-__device__ __forceinline__ float row_ror(float v) {
-  return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x120 + N, 0xF, 0xF, true));  // row_ror:N -> rotation within the row of 16 lanes
-}
-
-// device-side status: abort_flag[0] abort flag (zeroed before every launch), abort_flag[2] running count of hand-off
-// re-polls (diagnostics, aslp_lstm_seq_polls); host_err: mapped host word, counts timeouts
-struct SeqStatus {
-  unsigned *abort_flag;
-  unsigned *host_err;
-  unsigned long long *timing;  // diagnostics (devtools): NULL, or 8 accumulators of 10 ns ticks written by workgroup 0, wave 0
-  unsigned long long *trace;   // diagnostics (devtools): NULL, or [workgroup][2] entry / exit clock of the latest launch
-  unsigned epoch;              // launch counter (28 bits, never 0): tags the placement table entries of this launch
-  unsigned wave_collect;       // LSTM forward.  bit 0: every wave collects the K slice of m(t-1) it multiplies itself (no workgroup barrier behind the
-                               // collection); bit 1: operand reads pinned four fragments ahead of the products
-};
-__device__ __forceinline__ long tick(const SeqStatus &st) { return st.timing ? (long)wall_clock64() : 0; }
-// The phase accumulators live in LDS while the kernel runs (a fire-and-forget ds_add per mark): accumulating in global memory put an L2
-// round trip and a wait behind every mark -- 0.1-0.2 us charged to the NEXT phase, five times per timestep, and workgroup 0 (hence the
-// whole lock-stepped chain) ran that much slower under the timer.  timing_flush adds them to st.timing once, at the end.
-__shared__ unsigned long long g_tacc[8];
-__device__ __forceinline__ void timing_begin(const SeqStatus &st) {
-  if (st.timing && threadIdx.x < 8) g_tacc[threadIdx.x] = 0ull;   // (chain_role's barrier publishes it)
-}
-__device__ __forceinline__ void timing_flush(const SeqStatus &st) {   // caller: st.timing != NULL, workgroup 0, thread 0, behind the loop's last barrier
-  for (int k = 1; k <= 5; k++) st.timing[k] += g_tacc[k];
-}
-__device__ __forceinline__ void tock(const SeqStatus &st, int slot, long &t) {
-  if (!st.timing) return;
-  const long now = (long)wall_clock64();
-  if (blockIdx.x == 0 && threadIdx.x == 0) __hip_atomic_fetch_add(&g_tacc[slot], (unsigned long long)(now - t), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-  t = now;
-}
-
-// the same for the first thread of the gate role (thread 256) of the wave-specialised kernel
-__device__ __forceinline__ void tock_gate(const SeqStatus &st, int slot, long &t) {
-  if (!st.timing) return;
-  const long now = (long)wall_clock64();
-  if (blockIdx.x == 0 && threadIdx.x == 256) __hip_atomic_fetch_add(&g_tacc[slot], (unsigned long long)(now - t), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-  t = now;
-}
-
-// Bounded spin bookkeeping shared by the two phases below: false = give up (device-wide abort or 2 s without progress).
-__device__ __forceinline__ bool spin_ok(unsigned spins, long &t0, const SeqStatus &st) {
-  if ((spins & 31u) != 31u) return true;
-  if (__hip_atomic_load(st.abort_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) return false;
-  const long now = (long)wall_clock64();
-  if (t0 == 0) { t0 = now; return true; }
-  if (now - t0 <= kSpinLimitTicks) return true;
-  if ((threadIdx.x & 63) == 0) {
-    __hip_atomic_store(st.abort_flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_fetch_add(st.host_err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  }
-  return false;
-}
-
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef _Float16 half4 __attribute__((ext_vector_type(4)));
-// C/D layout of v_mfma_f32_16x16x4_f32: element e of lane l is row 4 * (l >> 4) + e, column l & 15
-constexpr int kTP = 17;  // LDS pitch of a 16 x 16 partial tile
-__device__ __forceinline__ void store_tile16(float *tile, const f32x4 &acc, int lane) {
-  const int n = lane & 15, r0 = 4 * (lane >> 4);
-  tile[(r0 + 0) * kTP + n] = acc.x;
-  tile[(r0 + 1) * kTP + n] = acc.y;
-  tile[(r0 + 2) * kTP + n] = acc.z;
-  tile[(r0 + 3) * kTP + n] = acc.w;
-}
-
-// ---- chain geometry shared by both kernels ------------------------------------------------------------------------
-constexpr int kFirstK = 256;       // largest K of a first-step product served inside the forward launch (aslp_lstm_seq_dir.w_first)
-constexpr int kChainStreams = 8;   // streams per chain (rows 0..7 of the 16-row MFMA tile; rows 8..15 repeat them, outputs unused)
-constexpr int kCellsPerWg = 16;
-constexpr int kMaxChains = 8;      // = XCDs of the chip: workgroup b serves chain b & 7
-constexpr int kMaxWgPerChain = 32; // = CUs of one XCD (C <= 512)
-
-struct ChainRole {
-  int dir, s0, c0;   // direction, first stream, first cell
-  bool active;       // this workgroup has a chain to serve
-  bool local;        // the chain's workgroups share one XCD (one L2): plain stores suffice
-};
-
-// Who am I, and does my chain sit on one XCD?  place: [kMaxChains][kMaxWgPerChain] words; an entry counts once it carries
-// this launch's epoch (a host-side launch counter, st.epoch) -- nothing to clear between launches.
-__device__ __forceinline__ ChainRole chain_role(int S, int ndir, int C, const SeqStatus &st, unsigned *place, int *lds_flag) {
-  ChainRole r;
-  const int chain = blockIdx.x & (kMaxChains - 1), cb = blockIdx.x >> 3;
-  const int nsg = (S + kChainStreams - 1) / kChainStreams, nchains = ndir * nsg, wpc = (C + kCellsPerWg - 1) / kCellsPerWg;
-  r.active = chain < nchains;
-  r.dir = r.active ? chain % ndir : 0;
-  r.s0 = (r.active ? chain / ndir : 0) * kChainStreams;
-  r.c0 = cb * kCellsPerWg;
-  r.local = false;
-  if (!r.active) return r;
-  if (threadIdx.x < 64) {  // wave 0
-    unsigned xcc;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-    xcc = (xcc & 15u) | (st.epoch << 4);  // entries of earlier launches carry another epoch = "not yet written"
-    unsigned *row = place + chain * kMaxWgPerChain;
-    if (threadIdx.x == 0) __hip_atomic_store(row + cb, xcc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const int l = threadIdx.x;
-    unsigned v = xcc;
-    long t0 = 0;
-    bool ok = true;
-    for (unsigned spins = 0;; spins++) {
-      if (l < wpc) v = __hip_atomic_load(row + l, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (!__any(l < wpc && (v >> 4) != st.epoch)) break;
-      if (!spin_ok(spins, t0, st)) { ok = false; break; }
-      __builtin_amdgcn_s_sleep(4);
-    }
-    const bool same = __all(l >= wpc || v == xcc);
-    if (threadIdx.x == 0) *lds_flag = !ok ? -1 : (same ? 1 : 0);
-  }
-  __syncthreads();
-  const int f = *lds_flag;
-  if (f < 0) r.active = false;  // timed out waiting for the chain to show up: abort word is set, leave
-  r.local = f == 1;
-  return r;
-}
-
-// The gate non-linearities on the hardware's exp2 and reciprocal (v_exp_f32, v_rcp_f32: 1 ulp each) instead of the correctly rounded
-// expf and division of sigmoid_ref / tanh_ref: ~6 instructions on the sequential path of a timestep instead of ~60, results within a
-// few ulp (1e-6 relative after T = 60 steps; the parity bar is 1e-4).  Default; ASLP_LSTM_FAST_ACT=0 keeps the exact forms (A/B).
-template <bool FAST>
-__device__ __forceinline__ float act_sigmoid(float x) {
-  if (!FAST) return sigmoid_ref(x);
-  const float e = __builtin_amdgcn_exp2f(-1.44269504088896340736f * fabsf(x));
-  return (x > 0.0f ? 1.0f : e) * __builtin_amdgcn_rcpf(1.0f + e);
-}
-template <bool FAST>
-__device__ __forceinline__ float act_tanh(float x) {
-  if (!FAST) return tanh_ref(x);
-  const float e2 = __builtin_amdgcn_exp2f(-2.88539008177792681472f * fabsf(x));   // exp(-2 |x|)
-  const float q = 2.0f * __builtin_amdgcn_rcpf(1.0f + e2);
-  return x > 0.0f ? -1.0f + q : 1.0f - q;
-}
 
 // ---- forward -------------------------------------------------------------------------------------------------------
 // grid 8 * ceil(C / 16) workgroups of 512 threads.  KW: K values per wave (C <= 8 * KW).
@@ -268,15 +100,7 @@ __global__ void __launch_bounds__(512) lstm_seq_fwd(aslp_lstm_seq a, SeqStatus s
   }
   // W_first rows of this workgroup's 64 gate columns -> LDS (zero where the column or k does not exist); read at step 0 only
   const bool first_in_kernel = D.w_first != nullptr && D.k_first > 0 && D.k_first <= kFirstK && D.k_first <= KMAX;   // r(0) is staged in m_lds rows of KMAX floats
-  if (first_in_kernel) {
-    const int kq = (D.k_first + 3) >> 2;   // 16-byte pieces per row
-    for (int p = threadIdx.x; p < 64 * kq; p += 512) {
-      const int n = p / kq, k0 = 4 * (p % kq), gate = n >> 4, cellb = c0 + (n & 15);
-      const bool ok = gate < G && cellb < C;
-      *reinterpret_cast<f32x4 *>(&wf_lds[n][k0]) = ok ? *reinterpret_cast<const f32x4 *>(D.w_first + (long)(gate * C + cellb) * D.ldw_first + k0)
-                                                      : f32x4{0.f, 0.f, 0.f, 0.f};
-    }
-  }
+  if (first_in_kernel) fwd_stage_w_first<G>(wf_lds, D.w_first, D.ldw_first, D.k_first, C, c0);
   // collection role.  Workgroup-wide: pieces tid and tid + 512 of [stream][C / 4], a barrier, then every wave reads its K slice.
   // Wave-local (st.wave_collect): a wave fetches exactly what it multiplies -- the 8 streams' pieces of its own K slice [kb, kb + kw),
   // 2 kw <= 128 pieces, lanes 0..63 take pieces lane and lane + 64 of [stream][kw / 4] -- so no other wave's data is involved, the
@@ -327,18 +151,12 @@ __global__ void __launch_bounds__(512) lstm_seq_fwd(aslp_lstm_seq a, SeqStatus s
     bool ok = true;
     const bool first_special = step == 0 && first_in_kernel;
     const bool product = !first_special && !(step == 0 && D.skip_first_product);
-    if (first_special) {   // r(0) of the chain's streams -> LDS (the history row block: stored before the launch, no hand-off)
-      const int kq = D.k_first >> 2;
-      for (int p = threadIdx.x; p < kChainStreams * kq; p += 512) {
-        const int sp = p / kq, k0 = 4 * (p % kq);
-        *reinterpret_cast<f32x4 *>(&m_lds[sp][k0]) =
-            *reinterpret_cast<const f32x4 *>(D.y + ((long)tp * S + min(s0 + sp, SE - 1)) * ld + D.col_first + k0);
-      }
-    }
+    if (first_special) fwd_stage_r0(m_lds, D.y, D.col_first, D.k_first, tp, S, ld, s0, SE);   // r(0) of the chain's streams -> LDS (the history row block: stored before the launch, no hand-off)
     if (product) {
       // 1. m(t-1) of the chain's streams -> LDS
       const __amdgpu_buffer_rsrc_t rs = make_rsrc(D.y + (long)tp * S * ld);
       u32x4 v0 = {0u, 0u, 0u, 0u}, v1 = {0u, 0u, 0u, 0u};
+      // (this wait as a shared function, ok returned or by reference: lstm_seq_fwd<false,16,true> 121 -> 123 VGPRs, 8 -> 2 spilled SGPRs; stays a copy, as in lstm_seq_fwd_h)
       long t0 = 0;
       for (unsigned spins = 0;; spins++) {
         if (h0) v0 = __builtin_amdgcn_raw_buffer_load_b128(rs, off0, 0, kAuxSc1);
@@ -353,6 +171,7 @@ __global__ void __launch_bounds__(512) lstm_seq_fwd(aslp_lstm_seq a, SeqStatus s
       if (h1) *reinterpret_cast<u32x4 *>(&m_lds[st1][4 * kq1]) = v1;
     }
     tock(st, 1, tm);  // collection
+    // (posting through a shared function: lstm_seq_fwd<true,64,false> 29 -> 30 spilled SGPRs, lstm_seq_fwd_h<false,1,false,1> 28 -> 29; stays a copy in all four kernels)
     if (lane == 0) fail[par][wave] = ok ? 0 : 1;
     if (!wave_collect || first_special) __syncthreads();   // (uniform) wave-local collection: this wave reads back only what it stored itself
     else __builtin_amdgcn_wave_barrier();
@@ -420,6 +239,7 @@ __global__ void __launch_bounds__(512) lstm_seq_fwd(aslp_lstm_seq a, SeqStatus s
         }
       }
     }
+    // (this store as a shared function: lstm_seq_fwd<true,16,true> 123 -> 127 VGPRs; stays a copy, as in lstm_seq_fwd_h)
     // result register r of a lane = stream 4 qs + r of tile column 32 h + 4 qc + jl
 #pragma unroll
     for (int h = 0; h < 2; h++) {
@@ -436,6 +256,7 @@ __global__ void __launch_bounds__(512) lstm_seq_fwd(aslp_lstm_seq a, SeqStatus s
       for (int w = 0; w < 8; w++) f |= fail[par][w];
       if (f) return;  // uniform: every wave reads the same eight words
     }
+    // (the gate block as a shared function of scalars: lstm_seq_fwd<true,16,true> 123 -> 117 VGPRs, 10 -> 14 spilled SGPRs; stays a copy, as in lstm_seq_fwd_h)
     float pre = 0.f;
     if (role < G) {
       pre = red[par][0][sl][role * 16 + cc];
@@ -478,6 +299,7 @@ __global__ void __launch_bounds__(512) lstm_seq_fwd(aslp_lstm_seq a, SeqStatus s
     cprev = cellv;
     tock(st, 5, tm);  // epilogue
   }
+  // (this tail as a shared function, whole or the trace / polls half: lstm_seq_fwd<false,64,true> 44 -> 51 spilled SGPRs, lstm_seq_bwd_h<true,1,1> 15 -> 13; stays a copy in all four kernels)
   if (st.timing && blockIdx.x == 0 && threadIdx.x == 0) {
     timing_flush(st); st.timing[0] += (unsigned long long)T; st.timing[6] += R.local ? 1ull : 0ull;
     st.timing[7] += (unsigned long long)((long)wall_clock64() - t_entry);   // this workgroup's whole stay, entry to exit
@@ -588,15 +410,7 @@ __global__ void __launch_bounds__(512) lstm_seq_fwd_h(aslp_lstm_seq a, SeqStatus
   }
   // W_first rows of this workgroup's 64 gate columns -> LDS (zero where the column or k does not exist); read at step 0 only
   const bool first_in_kernel = D.w_first != nullptr && D.k_first > 0 && D.k_first <= kFirstK && D.k_first <= KMAX;   // r(0) is staged in m_lds rows of KMAX floats
-  if (first_in_kernel) {
-    const int kq = (D.k_first + 3) >> 2;   // 16-byte pieces per row
-    for (int p = threadIdx.x; p < 64 * kq; p += 512) {
-      const int n = p / kq, k0 = 4 * (p % kq), gate = n >> 4, cellb = c0 + (n & 15);
-      const bool ok = gate < G && cellb < C;
-      *reinterpret_cast<f32x4 *>(&wf_lds[n][k0]) = ok ? *reinterpret_cast<const f32x4 *>(D.w_first + (long)(gate * C + cellb) * D.ldw_first + k0)
-                                                      : f32x4{0.f, 0.f, 0.f, 0.f};
-    }
-  }
+  if (first_in_kernel) fwd_stage_w_first<G>(wf_lds, D.w_first, D.ldw_first, D.k_first, C, c0);
   // collection role.  Workgroup-wide: pieces tid and tid + 512 of [stream][C / 4], a barrier, then every wave reads its K slice.
   // Wave-local (st.wave_collect): a wave fetches exactly what it multiplies -- the 8 streams' pieces of its own K slice [kb, kb + kw),
   // 2 kw <= 128 pieces, lanes 0..63 take pieces lane and lane + 64 of [stream][kw / 4] -- so no other wave's data is involved, the
@@ -648,14 +462,7 @@ __global__ void __launch_bounds__(512) lstm_seq_fwd_h(aslp_lstm_seq a, SeqStatus
     bool ok = true;
     const bool first_special = step == 0 && first_in_kernel;
     const bool product = !first_special && !(step == 0 && D.skip_first_product);
-    if (first_special) {   // r(0) of the chain's streams -> LDS (the history row block: stored before the launch, no hand-off)
-      const int kq = D.k_first >> 2;
-      for (int p = threadIdx.x; p < kChainStreams * kq; p += 512) {
-        const int sp = p / kq, k0 = 4 * (p % kq);
-        *reinterpret_cast<f32x4 *>(&m_lds[sp][k0]) =
-            *reinterpret_cast<const f32x4 *>(D.y + ((long)tp * S + min(s0 + sp, SE - 1)) * ld + D.col_first + k0);
-      }
-    }
+    if (first_special) fwd_stage_r0(m_lds, D.y, D.col_first, D.k_first, tp, S, ld, s0, SE);   // r(0) of the chain's streams -> LDS (the history row block: stored before the launch, no hand-off)
     if (product) {
       // 1. m(t-1) of the chain's streams -> LDS
       const __amdgpu_buffer_rsrc_t rs = make_rsrc(D.y + (long)tp * S * ld);
@@ -968,6 +775,7 @@ __global__ void __launch_bounds__(512) lstm_seq_bwd(aslp_lstm_seq a, SeqStatus s
         const int i0 = threadIdx.x, i1 = threadIdx.x + 512;
         const bool h0 = i0 < npiece, h1 = i1 < npiece;
         u32x4 v0 = {0u, 0u, 0u, 0u}, v1 = {0u, 0u, 0u, 0u};
+        // (this wait as a shared function: lstm_seq_bwd_h<true,1,1> 82 -> 81 VGPRs, 15 -> 7 spilled SGPRs; with reset and drain around a lambda the same; stays a copy, as in lstm_seq_bwd_h)
         long t0 = 0;
         for (unsigned spins = 0;; spins++) {
           if (h0) v0 = __builtin_amdgcn_raw_buffer_load_b128(rs, i0 * 16, 0, kAuxSc1);
@@ -1009,26 +817,14 @@ __global__ void __launch_bounds__(512) lstm_seq_bwd(aslp_lstm_seq a, SeqStatus s
         for (int p = 0; p < wpc; p++) psum += shares[p * 128 + base];
         dm += psum;
       }
-      const float dh = dtanh(yh, dm * yo);
-      const float dov = dsigm(yo, dm * yh);
-      float dc = dh + dn_c * yn_f;
-      if (!CIFG) dc += dn_i * pi;
-      dc += dn_f * pf;
-      dc += dov * po;
-      float dg, df, di = 0.f;
-      if (!CIFG) {
-        df = dsigm(yf, dc * cprev);
-        di = dsigm(yi, dc * yg);
-        dg = dtanh(yg, dc * yi);
-      } else {
-        df = dsigm(yf, dc * cprev - dc * yg);
-        dg = dtanh(yg, dc - dc * yf);
-      }
+      const BwdDiffs r = bwd_gate_diffs<CIFG>(dm, yo, yh, yg, yf, yi, yn_f, cprev, dn_c, dn_f, dn_i, pf, po, pi);
+      const float dh = r.dh, dov = r.dov, dc = r.dc, dg = r.dg, df = r.df, di = r.di;
       // the next step's left operand stays here; the buffer copy is for the batched products after the launch
       float *mine = &own_dg[par][sl][cc];
       mine[0] = dg;
       if (!CIFG) { mine[16] = di; mine[32] = df; mine[48] = dov; }
       else { mine[16] = df; mine[32] = dov; }
+      // (these stores and sums as a shared function of scalars: lstm_seq_bwd_h<false,1,1> 20 -> 21 spilled SGPRs; stays a copy, as in lstm_seq_bwd_h)
       if (live) {
         D.d[o_ + og + cell] = dg; D.d[o_ + of + cell] = df; D.d[o_ + oo + cell] = dov;
         if (!CIFG) D.d[o_ + oi + cell] = di;
@@ -1280,21 +1076,8 @@ __global__ void __launch_bounds__(512) lstm_seq_bwd_h(aslp_lstm_seq a, SeqStatus
       if (step > 0)   // the chain's shares of this pair, already added up: [row group][odd register][column][register pair] (see the publication)
         dm += dmsum[(((sl >> 2) * 2 + (sl & 1)) * 16 + cc) * 2 + ((sl & 3) >> 1)];
       tock(st, 3, tm);  // (devtools) shares summed
-      const float dh = dtanh(yh, dm * yo);
-      const float dov = dsigm(yo, dm * yh);
-      float dc = dh + dn_c * yn_f;
-      if (!CIFG) dc += dn_i * pi;
-      dc += dn_f * pf;
-      dc += dov * po;
-      float dg, df, di = 0.f;
-      if (!CIFG) {
-        df = dsigm(yf, dc * cprev);
-        di = dsigm(yi, dc * yg);
-        dg = dtanh(yg, dc * yi);
-      } else {
-        df = dsigm(yf, dc * cprev - dc * yg);
-        dg = dtanh(yg, dc - dc * yf);
-      }
+      const BwdDiffs r = bwd_gate_diffs<CIFG>(dm, yo, yh, yg, yf, yi, yn_f, cprev, dn_c, dn_f, dn_i, pf, po, pi);
+      const float dh = r.dh, dov = r.dov, dc = r.dc, dg = r.dg, df = r.df, di = r.di;
       // the next step's left operand stays here; the buffer copy is for the batched products after the launch
       {
         // this stream's gate diffs, scaled by the power of two that puts the largest of its 16 * G in [2^13, 2^14), as two fp16 pieces
@@ -1830,16 +1613,13 @@ bool fast_act() {   // A/B switch: ASLP_LSTM_FAST_ACT=0 keeps the correctly roun
   static const bool off = getenv("ASLP_LSTM_FAST_ACT") != nullptr && getenv("ASLP_LSTM_FAST_ACT")[0] == '0';
   return !off;
 }
-SeqKernel pick_fwd(bool cifg, int C) {
-  if (fast_act()) {
-    if (C <= 128) return cifg ? lstm_seq_fwd<true, 16, true> : lstm_seq_fwd<false, 16, true>;
-    if (C <= 512) return cifg ? lstm_seq_fwd<true, 64, true> : lstm_seq_fwd<false, 64, true>;
-    return nullptr;
-  }
-  if (C <= 128) return cifg ? lstm_seq_fwd<true, 16, false> : lstm_seq_fwd<false, 16, false>;
-  if (C <= 512) return cifg ? lstm_seq_fwd<true, 64, false> : lstm_seq_fwd<false, 64, false>;
+template <bool FAST>
+SeqKernel pick_fwd_act(bool cifg, int C) {
+  if (C <= 128) return cifg ? lstm_seq_fwd<true, 16, FAST> : lstm_seq_fwd<false, 16, FAST>;
+  if (C <= 512) return cifg ? lstm_seq_fwd<true, 64, FAST> : lstm_seq_fwd<false, 64, FAST>;
   return nullptr;
 }
+SeqKernel pick_fwd(bool cifg, int C) { return fast_act() ? pick_fwd_act<true>(cifg, C) : pick_fwd_act<false>(cifg, C); }
 // product on fp16 matrix instructions with two-piece fp32-equivalent operands (lstm_seq_fwd_h): A/B switch ASLP_LSTM_SPLIT_F16
 int g_lstm_split_override = -1;   // aslp_lstm_split16(): -1 = the environment decides
 bool split_f16_on() {   // default on; ASLP_LSTM_SPLIT_F16=0 puts the recurrent products back on the fp32 instruction (lstm_seq_fwd / lstm_seq_bwd)
@@ -1853,17 +1633,14 @@ int lstm_pieces() {
   static const int env = (getenv("ASLP_LSTM_PIECES") != nullptr && getenv("ASLP_LSTM_PIECES")[0] == '1' && getenv("ASLP_LSTM_PIECES")[1] == 0) ? 1 : 2;
   return g_lstm_pieces_override > 0 ? g_lstm_pieces_override : env;
 }
-template <int NP>
-SeqKernel pick_fwd_h_np(bool cifg, int C) {
-  if (fast_act()) {
-    if (C <= 256) return cifg ? lstm_seq_fwd_h<true, 1, true, NP> : lstm_seq_fwd_h<false, 1, true, NP>;
-    if (C <= 512) return cifg ? lstm_seq_fwd_h<true, 2, true, NP> : lstm_seq_fwd_h<false, 2, true, NP>;
-    return nullptr;
-  }
-  if (C <= 256) return cifg ? lstm_seq_fwd_h<true, 1, false, NP> : lstm_seq_fwd_h<false, 1, false, NP>;
-  if (C <= 512) return cifg ? lstm_seq_fwd_h<true, 2, false, NP> : lstm_seq_fwd_h<false, 2, false, NP>;
+template <int NP, bool FAST>
+SeqKernel pick_fwd_h_act(bool cifg, int C) {
+  if (C <= 256) return cifg ? lstm_seq_fwd_h<true, 1, FAST, NP> : lstm_seq_fwd_h<false, 1, FAST, NP>;
+  if (C <= 512) return cifg ? lstm_seq_fwd_h<true, 2, FAST, NP> : lstm_seq_fwd_h<false, 2, FAST, NP>;
   return nullptr;
 }
+template <int NP>
+SeqKernel pick_fwd_h_np(bool cifg, int C) { return fast_act() ? pick_fwd_h_act<NP, true>(cifg, C) : pick_fwd_h_act<NP, false>(cifg, C); }
 template <int NP>
 SeqKernelB pick_bwd_h_np(bool cifg, int C) {
   if (C <= 128) return cifg ? lstm_seq_bwd_h<true, 1, NP> : lstm_seq_bwd_h<false, 1, NP>;
@@ -1915,9 +1692,6 @@ bool grid_fits(const void *k, int threads, long blocks) {
   if (occ < 1) return false;
   return blocks <= (long)rt.num_cu * (occ >= 2 ? occ - 1 : 1);
 }
-// Streams per chain a launch with these arguments uses (half chains of 4 streams, two workgroups per CU, were measured level with the chains
-// of 8 and are gone: DESIGN 4a)
-int chain_streams_for(const aslp_lstm_seq *, bool) { return kChainStreams; }
 
 }  // namespace
 bool device_shared() { return device_gate().on; }   // (scratch.h)
@@ -1950,7 +1724,7 @@ int aslp_lstm_seq_first_product_supported(int k_first) { return k_first > 0 && k
 int aslp_lstm_seq_first_product_supported_for(int k_first, int C) {
   return aslp_lstm_seq_first_product_supported(k_first) && k_first <= (C <= 128 ? 128 : 512);
 }
-int aslp_lstm_seq_chain_streams(const aslp_lstm_seq *a, int backward) { return seq_args_ok(a) ? chain_streams_for(a, backward != 0) : kChainStreams; }
+int aslp_lstm_seq_chain_streams(const aslp_lstm_seq * /*a*/, int /*backward*/) { return kChainStreams; }
 
 void aslp_lstm_seq_fill(float *buf, int ld, int T, int S, int col0, int ncols) {
   if (!buf || T <= 0 || S <= 0 || ld <= 0) return;
@@ -2098,8 +1872,7 @@ static bool fill_vec_grad_args(SeqVecGradArgs &g, const aslp_lstm_seq *a, int di
       !peep_o_corr || !peep_o || (!a->cifg && (!peep_i_corr || !peep_i)))
     return false;
   g.partial = a->grad_partial; g.ld = a->grad_ld; g.ndir = a->ndir; g.dir = dir;
-  const int cs = chain_streams_for(a, true);
-  g.nsg = ((a->s_count > 0 ? a->s_count : a->S) + cs - 1) / cs;
+  g.nsg = ((a->s_count > 0 ? a->s_count : a->S) + kChainStreams - 1) / kChainStreams;
   g.C = a->C; g.cifg = a->cifg; g.mmt = mmt; g.clip = clip; g.neg_lr = neg_lr;
   const int C = a->C;
   // gate order of the buffer: g, i, f, o (cifg: g, f, o)
