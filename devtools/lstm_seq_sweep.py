@@ -35,31 +35,13 @@ CASES = [(68, 5, 1, 1, 0, 0, 0, 0, 1, (0, 0)),
          (512, 9, 1, 2, 0, 1, 40, 0, 1, (3, 5))]
 
 
-class SeqDir(C.Structure):   # aslp_lstm_seq_dir (include/aslp_kernels.h)
-    _fields_ = [("y", C.c_void_p), ("d", C.c_void_p), ("w", C.c_void_p), ("peep_i", C.c_void_p), ("peep_f", C.c_void_p), ("peep_o", C.c_void_p),
-                ("seq_lengths", C.c_void_p), ("reverse", C.c_int), ("skip_first_product", C.c_int), ("w_first", C.c_void_p),
-                ("ldw_first", C.c_int), ("k_first", C.c_int), ("col_first", C.c_int)]
-
-
-class Seq(C.Structure):      # aslp_lstm_seq
-    _fields_ = [("dir", SeqDir * 2), ("ndir", C.c_int), ("ld", C.c_int), ("ldw", C.c_int), ("T", C.c_int), ("S", C.c_int), ("C", C.c_int),
-                ("cifg", C.c_int), ("grad_partial", C.c_void_p), ("grad_ld", C.c_int), ("s_begin", C.c_int), ("s_count", C.c_int),
-                ("dmax_parts", C.c_void_p * 2)]
-
-
 def child(path, label):
     import torch
     sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
     import aslp_import
     aslp = aslp_import.load()
     lib, ops = aslp.lib, aslp.ops
-    for name in ("aslp_lstm_seq_supported", "aslp_lstm_seq_last_dmax"):
-        getattr(lib, name).restype = C.c_int
-    lib.aslp_lstm_seq_supported.argtypes = [C.POINTER(Seq), C.c_int]
-    for name in ("aslp_lstm_seq_forward", "aslp_lstm_seq_backward"):
-        getattr(lib, name).argtypes, getattr(lib, name).restype = [C.POINTER(Seq)], None
-    lib.aslp_lstm_seq_fill.argtypes, lib.aslp_lstm_seq_fill.restype = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int], None
-    lib.aslp_lstm_split16.argtypes, lib.aslp_lstm_split16.restype = [C.c_int], None
+    Seq = aslp._lib.Seq   # the structures and the signatures of aslp_lstm_seq_* live with the binding (kaldi-aslp_amd/_lib.py)
     dev = torch.device("cuda:0")
     ops.use_torch_stream()
 

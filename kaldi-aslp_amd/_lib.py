@@ -39,6 +39,20 @@ class GruSeq(C.Structure):
                 ("ld", C.c_int), ("T", C.c_int), ("S", C.c_int), ("H", C.c_int), ("s_begin", C.c_int), ("s_count", C.c_int)]
 
 
+class SeqDir(C.Structure):
+    """aslp_lstm_seq_dir (include/aslp_kernels.h)"""
+    _fields_ = [("y", C.c_void_p), ("d", C.c_void_p), ("w", C.c_void_p), ("peep_i", C.c_void_p), ("peep_f", C.c_void_p), ("peep_o", C.c_void_p),
+                ("seq_lengths", C.c_void_p), ("reverse", C.c_int), ("skip_first_product", C.c_int), ("w_first", C.c_void_p),
+                ("ldw_first", C.c_int), ("k_first", C.c_int), ("col_first", C.c_int)]
+
+
+class Seq(C.Structure):
+    """aslp_lstm_seq (include/aslp_kernels.h)"""
+    _fields_ = [("dir", SeqDir * 2), ("ndir", C.c_int), ("ld", C.c_int), ("ldw", C.c_int), ("T", C.c_int), ("S", C.c_int), ("C", C.c_int),
+                ("cifg", C.c_int), ("grad_partial", C.c_void_p), ("grad_ld", C.c_int), ("s_begin", C.c_int), ("s_count", C.c_int),
+                ("dmax_parts", C.c_void_p * 2)]
+
+
 class RnnVecGrad(C.Structure):
     """aslp_rnn_vec_grad (include/aslp_kernels.h)"""
     _fields_ = [("d", C.c_void_p), ("x", C.c_void_p), ("ldx", C.c_int), ("n", C.c_int), ("corr", C.c_void_p), ("param", C.c_void_p)]
@@ -165,6 +179,13 @@ _sig("aslp_lstm_operand_pieces", None, _i)
 _sig("aslp_lstm_operand_pieces_get", _i)
 _sig("aslp_lstm_seq_last_pieces", _i)
 _sig("aslp_lstm_seq_timing", None, _i, C.POINTER(C.c_ulonglong))
+_sig("aslp_lstm_seq_supported", _i, C.POINTER(Seq), _i)
+_sig("aslp_lstm_seq_first_product_supported_for", _i, _i, _i)
+_sig("aslp_lstm_seq_fill", None, _vp, _i, _i, _i, _i, _i)
+_sig("aslp_lstm_seq_forward", None, C.POINTER(Seq))
+_sig("aslp_lstm_seq_backward", None, C.POINTER(Seq))
+_sig("aslp_lstm_seq_last_dmax", _i)
+_sig("aslp_lstm_split16", None, _i)
 _sig("aslp_region_profile", None, _i)
 _sig("aslp_region_reset", None)
 _sig("aslp_region_get", C.c_long, C.c_char_p, C.POINTER(C.c_double))

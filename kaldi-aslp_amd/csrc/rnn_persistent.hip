@@ -854,7 +854,7 @@ __global__ void __launch_bounds__(512) lstm_seq_bwd(aslp_lstm_seq a, SeqStatus s
       float v = gl[k * 16 + c];
 #pragma unroll
       for (int q = 1; q < kChainStreams; q++) v += gl[(q * 7 + k) * 16 + c];
-      if (c0 + c < C) a.grad_partial[((long)chain * 7 + k) * a.grad_ld + c0 + c] = v;
+      if (c0 + c < C && !(CIFG && (k == 1 || k == 4))) a.grad_partial[((long)chain * 7 + k) * a.grad_ld + c0 + c] = v;   // (no d_i rows with coupled gates: left as they are)
     }
   }
   if (st.timing && blockIdx.x == 0 && threadIdx.x == 0) { timing_flush(st); st.timing[0] += (unsigned long long)T; st.timing[6] += R.local ? 1ull : 0ull; }
@@ -1130,7 +1130,7 @@ __global__ void __launch_bounds__(512) lstm_seq_bwd_h(aslp_lstm_seq a, SeqStatus
       float v = gl[k * 16 + c];
 #pragma unroll
       for (int q = 1; q < kChainStreams; q++) v += gl[(q * 7 + k) * 16 + c];
-      if (c0 + c < C) a.grad_partial[((long)chain * 7 + k) * a.grad_ld + c0 + c] = v;
+      if (c0 + c < C && !(CIFG && (k == 1 || k == 4))) a.grad_partial[((long)chain * 7 + k) * a.grad_ld + c0 + c] = v;   // (no d_i rows with coupled gates: left as they are)
     }
   }
   if (a.dmax_parts[0] != nullptr || a.dmax_parts[1] != nullptr) {   // uniform.  (a dead lane's gate diffs are zeros: the row maximum is the live cells')

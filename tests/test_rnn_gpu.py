@@ -67,8 +67,12 @@ def oracle_step(oracle, marker, dirs, grads, x, od, T, S, state, lens, chunk, lr
 
 # (12, 16, 8, 5, 70): 70 streams are more than one persistent launch has chains for (32 bidirectional / 64 unidirectional): the engine
 # runs the recurrence in stream windows (aslp_lstm_seq.s_begin / s_count), 3 resp. 2 launches per pass
+# (24, 132, 68, 7, 9) / (24, 260, 132, 6, 33): cell counts strictly between the rungs of the persistent kernels' ladders (128 / 256 / 512), each
+# with a partial last workgroup, asserted to run there: the layer code around the kernels -- the W_eff product, the first step's r(0) W_r^T
+# inside the launch at R = 68 and 132, stream windows at S = 33 -- on the sizes tests/test_lstm_seq_kernels_gpu.py drives through the C ABI
+ON_PERSISTENT = [(24, 132, 68, 7, 9), (24, 260, 132, 6, 33)]
 @pytest.mark.parametrize("marker", list(FAMILY))
-@pytest.mark.parametrize("dims", [(5, 8, 4, 6, 3), (40, 64, 32, 12, 4), (33, 48, 17, 9, 5), (12, 16, 8, 5, 70)])
+@pytest.mark.parametrize("dims", [(5, 8, 4, 6, 3), (40, 64, 32, 12, 4), (33, 48, 17, 9, 5), (12, 16, 8, 5, 70)] + ON_PERSISTENT)
 def test_lstm_family_train_steps_match_oracle(aslp, oracle, dev, tmp_path, marker, dims):
     D, Cc, R, T, S = dims
     bidir, proj, cifg, lc, _ = FAMILY[marker]
@@ -101,9 +105,13 @@ def test_lstm_family_train_steps_match_oracle(aslp, oracle, dev, tmp_path, marke
             net.SetSeqLengths(lens)
         out_ref, idf_ref, state = oracle_step(oracle, marker, dirs, grads, x, od, T, S, state, lens, chunk, lr, mmt, clip)
         out = net.Propagate(torch.from_numpy(x).to(dev)).cpu().numpy()
+        if dims in ON_PERSISTENT:
+            assert aslp.lib.aslp_recurrent_last_path(0) == PERSISTENT, (marker, dims, "forward ran on path", aslp.lib.aslp_recurrent_last_path(0))
         assert oracle.rel_err(out, out_ref) < TOL and oracle.max_err(out, out_ref) < 10 * TOL, ("out", step)
         before = net.GetParams()
         idf = net.Backpropagate(torch.from_numpy(od).to(dev), want_in_diff=True).cpu().numpy()
+        if dims in ON_PERSISTENT:
+            assert aslp.lib.aslp_recurrent_last_path(1) == PERSISTENT, (marker, dims, "backward ran on path", aslp.lib.aslp_recurrent_last_path(1))
         assert oracle.rel_err(idf, idf_ref) < TOL and oracle.max_err(idf, idf_ref) < 10 * TOL, ("in_diff", step)
         after = net.GetParams()
         assert oracle.rel_err(after, flat()) < TOL and oracle.max_err(after, flat()) < 10 * TOL, ("params", step)
