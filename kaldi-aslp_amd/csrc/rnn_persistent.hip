@@ -33,8 +33,8 @@
 // The grid must be co-resident: aslp_lstm_seq_supported() checks it against the occupancy of the kernel with a margin
 // of one workgroup per CU, otherwise the caller keeps the one-launch-per-timestep path.
 //
-// rnn_seq_parts.h holds what the kernels here share: the file-scope parts (SeqStatus, timers, spin_ok, chain_role, the gate non-linearities ...) and
-// the parts of an LSTM timestep whose extraction left every kernel's instructions as they were; the rest stays in the kernels, with a note at its place.
+// rnn_seq_parts.h holds what the kernels here share: the file-scope parts (SeqStatus, timers, spin_ok, seq_failed, chain_role, the gate non-linearities
+// ...) and the parts of an LSTM timestep whose extraction left every kernel's resource table as it was; the rest stays in the kernels, with a note at its place.
 #include <fcntl.h>
 #include <sys/file.h>
 #include <unistd.h>
@@ -82,6 +82,7 @@ __global__ void __launch_bounds__(512) lstm_seq_fwd(aslp_lstm_seq a, SeqStatus s
   const int C = a.C, S = a.S, T = a.T, ld = a.ld;
   const int GC = G * C, oc = GC, oh = GC + C, om = GC + 2 * C;
   const int c0 = R.c0, s0 = a.s_begin + R.s0;
+  // (lane .. jl and pair .. sq below as one function returning a record: lstm_seq_bwd_h<true,1,1> 82 -> 80 VGPRs, occupancy 5 -> 6; stay copies in all four kernels)
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int qs = (lane >> 2) & 1, qc = lane >> 3, jl = lane & 3;
   const int kw = ((C + 31) / 32) * 4, kb = wave * kw;  // this wave's K range [kb, kb + kw), a multiple of 4 long
@@ -224,21 +225,7 @@ __global__ void __launch_bounds__(512) lstm_seq_fwd(aslp_lstm_seq a, SeqStatus s
       }
       }
     }
-    if (first_special) {   // r(0) W_first^T, both operands from LDS; this wave's slice of K = k_first
-      const int kwf = ((D.k_first + 31) / 32) * 4, kbf = wave * kwf;
-      const float *arow = &m_lds[4 * qs + jl][0];
-      for (int k0 = kbf; k0 < min(kbf + kwf, D.k_first); k0 += 4) {
-        const f32x4 av = *reinterpret_cast<const f32x4 *>(arow + k0);
-#pragma unroll
-        for (int h = 0; h < 2; h++) {
-          const f32x4 b = *reinterpret_cast<const f32x4 *>(&wf_lds[32 * h + 4 * qc + jl][k0]);
-          acc[h][0] = __builtin_amdgcn_mfma_f32_4x4x1f32(av.x, b.x, acc[h][0], 0, 0, 0);
-          acc[h][1] = __builtin_amdgcn_mfma_f32_4x4x1f32(av.y, b.y, acc[h][1], 0, 0, 0);
-          acc[h][0] = __builtin_amdgcn_mfma_f32_4x4x1f32(av.z, b.z, acc[h][0], 0, 0, 0);
-          acc[h][1] = __builtin_amdgcn_mfma_f32_4x4x1f32(av.w, b.w, acc[h][1], 0, 0, 0);
-        }
-      }
-    }
+    if (first_special) fwd_first_product(acc, m_lds, wf_lds, D.k_first, wave, qs, qc, jl);   // r(0) W_first^T, this wave's slice of K = k_first
     // (this store as a shared function: lstm_seq_fwd<true,16,true> 123 -> 127 VGPRs; stays a copy, as in lstm_seq_fwd_h)
     // result register r of a lane = stream 4 qs + r of tile column 32 h + 4 qc + jl
 #pragma unroll
@@ -250,12 +237,7 @@ __global__ void __launch_bounds__(512) lstm_seq_fwd(aslp_lstm_seq a, SeqStatus s
     tock(st, 2, tm);  // product
     __syncthreads();
     tock(st, 4, tm);
-    {
-      int f = 0;
-#pragma unroll
-      for (int w = 0; w < 8; w++) f |= fail[par][w];
-      if (f) return;  // uniform: every wave reads the same eight words
-    }
+    if (seq_failed(fail, par)) return;
     // (the gate block as a shared function of scalars: lstm_seq_fwd<true,16,true> 123 -> 117 VGPRs, 10 -> 14 spilled SGPRs; stays a copy, as in lstm_seq_fwd_h)
     float pre = 0.f;
     if (role < G) {
@@ -537,21 +519,7 @@ __global__ void __launch_bounds__(512) lstm_seq_fwd_h(aslp_lstm_seq a, SeqStatus
         }
       }
     }
-    if (first_special) {   // r(0) W_first^T, both operands from LDS; this wave's slice of K = k_first
-      const int kwf = ((D.k_first + 31) / 32) * 4, kbf = wave * kwf;
-      const float *arow = &m_lds[4 * qs + jl][0];
-      for (int k0 = kbf; k0 < min(kbf + kwf, D.k_first); k0 += 4) {
-        const f32x4 av = *reinterpret_cast<const f32x4 *>(arow + k0);
-#pragma unroll
-        for (int h = 0; h < 2; h++) {
-          const f32x4 b = *reinterpret_cast<const f32x4 *>(&wf_lds[32 * h + 4 * qc + jl][k0]);
-          acc[h][0] = __builtin_amdgcn_mfma_f32_4x4x1f32(av.x, b.x, acc[h][0], 0, 0, 0);
-          acc[h][1] = __builtin_amdgcn_mfma_f32_4x4x1f32(av.y, b.y, acc[h][1], 0, 0, 0);
-          acc[h][0] = __builtin_amdgcn_mfma_f32_4x4x1f32(av.z, b.z, acc[h][0], 0, 0, 0);
-          acc[h][1] = __builtin_amdgcn_mfma_f32_4x4x1f32(av.w, b.w, acc[h][1], 0, 0, 0);
-        }
-      }
-    }
+    if (first_special) fwd_first_product(acc, m_lds, wf_lds, D.k_first, wave, qs, qc, jl);   // r(0) W_first^T, this wave's slice of K = k_first
     if (product) {
       // rows 0..7 (lanes 0..31) hold m_hi w, rows 8..15 (lanes 32..63) m_lo' w of the same streams: m w = ([m_hi w] + 2^-11 [m_lo' w]) / sc.
       // One v_permlane32_swap joins the halves of TWO result registers at once: of (x, y) it leaves x's two halves in lanes 0..31 of the
@@ -585,12 +553,7 @@ __global__ void __launch_bounds__(512) lstm_seq_fwd_h(aslp_lstm_seq a, SeqStatus
     tock(st, 2, tm);  // product
     __syncthreads();
     tock(st, 4, tm);
-    {
-      int f = 0;
-#pragma unroll
-      for (int w = 0; w < 8; w++) f |= fail[par][w];
-      if (f) return;  // uniform: every wave reads the same eight words
-    }
+    if (seq_failed(fail, par)) return;
     float pre = 0.f;
     if (role < G) {
       pre = red[par][0][sl][role * 16 + cc];
@@ -718,6 +681,7 @@ __global__ void __launch_bounds__(512) lstm_seq_bwd(aslp_lstm_seq a, SeqStatus s
     const long o_ = ((long)t * S + sq) * ld;
     long tm = tick(st);
     float dm = 0.f, yo = 0.f, yh = 0.f, yg = 0.f, yf = 0.f, yi = 0.f, yn_f = 0.f, cprev = 0.f, ccur = 0.f;
+    // (these loads as a shared function: lstm_seq_bwd_h<true,1,1> 82 -> 80 VGPRs, occupancy 5 -> 6; stay a copy, as in lstm_seq_bwd_h)
     if (live) {  // everything that does not depend on the other workgroups, requested first
       dm = D.d[o_ + om + cq];
       yo = D.y[o_ + oo + cq]; yh = D.y[o_ + oh + cq]; yg = D.y[o_ + og + cq]; yf = D.y[o_ + of + cq];
@@ -804,12 +768,7 @@ __global__ void __launch_bounds__(512) lstm_seq_bwd(aslp_lstm_seq a, SeqStatus s
     if (lane == 0) fail[par][wave] = ok ? 0 : 1;
     __syncthreads();
     tock(st, 4, tm);
-    {
-      int f = 0;
-#pragma unroll
-      for (int w = 0; w < 8; w++) f |= fail[par][w];
-      if (f) return;
-    }
+    if (seq_failed(fail, par)) return;
     if (threadIdx.x < 128) {
       if (step > 0) {  // shares of my 16 cells, added in workgroup order
         float psum = 0.f;
@@ -842,6 +801,7 @@ __global__ void __launch_bounds__(512) lstm_seq_bwd(aslp_lstm_seq a, SeqStatus s
     tock(st, 5, tm);
     __syncthreads();  // own_dg[par] complete before anybody multiplies with it; shares[] free for the next collection
   }
+  // (this reduction as a shared function: lstm_seq_bwd<true,4> 60 -> 63 spilled SGPRs, or other FMAs in the time loop above; stays a copy, as in lstm_seq_bwd_h)
   if (a.grad_partial) {   // the chain's 8 streams meet in LDS (stream order), one row of 16 cells per quantity goes out per workgroup
     float *gl = shares;   // [stream 8][quantity 7][cell 16]: free after the loop's last barrier
     if (threadIdx.x < 128) {
@@ -1066,12 +1026,7 @@ __global__ void __launch_bounds__(512) lstm_seq_bwd_h(aslp_lstm_seq a, SeqStatus
     if (lane == 0) fail[par][wave] = ok ? 0 : 1;
     __syncthreads();
     tock(st, 4, tm);
-    {
-      int f = 0;
-#pragma unroll
-      for (int w = 0; w < 8; w++) f |= fail[par][w];
-      if (f) return;
-    }
+    if (seq_failed(fail, par)) return;
     if (threadIdx.x < 128) {
       if (step > 0)   // the chain's shares of this pair, already added up: [row group][odd register][column][register pair] (see the publication)
         dm += dmsum[(((sl >> 2) * 2 + (sl & 1)) * 16 + cc) * 2 + ((sl & 3) >> 1)];
@@ -1293,12 +1248,6 @@ __device__ __forceinline__ void gru_publish(const u32x4 &pk, float *rowblock, in
 }
 // K values per wave for a reduction of length K: a multiple of 8 (so that the split products' halves are whole fragments), 8 waves cover K
 __device__ __forceinline__ int gru_kw(int K) { return ((K + 63) / 64) * 8; }
-__device__ __forceinline__ bool gru_failed(const int (*fail)[8], int round) {
-  int f = 0;
-#pragma unroll
-  for (int w = 0; w < 8; w++) f |= fail[round][w];
-  return f != 0;  // uniform: every wave reads the same eight words
-}
 
 // grid 8 * ceil(H / 16) workgroups of 512 threads (chains >= S / 8 leave at once).  KW: K values per wave, H <= 8 * KW.
 template <int KW>
@@ -1342,7 +1291,7 @@ __global__ void __launch_bounds__(512) gru_seq_fwd(aslp_gru_seq a, SeqStatus st,
     __syncthreads();
     gru_store_wide(red[0], gru_product<NBW>(a_lds, MP, bw1, kb, kw, H, g), g);
     __syncthreads();
-    if (gru_failed(fail, 0)) return;
+    if (seq_failed(fail, 0)) return;
     float gate = 0.f;
     if (threadIdx.x < 256) gate = sigmoid_ref(xg + gru_sum_wide(red[0], g.sl, g.role * 16 + g.cc));
     const float zz = gate;                       // meaningful on lane 0 of the pair
@@ -1358,7 +1307,7 @@ __global__ void __launch_bounds__(512) gru_seq_fwd(aslp_gru_seq a, SeqStatus st,
     __syncthreads();
     gru_store_split(red[1], gru_product<NBS>(a_lds, MP, bw2, kbs, kw / 2, H, g), g);
     __syncthreads();
-    if (gru_failed(fail, 1)) return;
+    if (seq_failed(fail, 1)) return;
     float mm = 0.f, hh = 0.f;
     if (threadIdx.x < 256 && g.role == 0) {
       mm = tanh_ref(xm + gru_sum_split(red[1], g.sl, g.cc));
@@ -1419,7 +1368,7 @@ __global__ void __launch_bounds__(512) gru_seq_bwd(aslp_gru_seq a, SeqStatus st,
     __syncthreads();
     if (step > 0) gru_store_split(red[0], gru_product<NB1>(a_lds, MP, bwa, k1, kw1 / 2, 2 * H, g), g);
     __syncthreads();
-    if (gru_failed(fail, 0)) return;
+    if (seq_failed(fail, 0)) return;
     float dh = 0.f, dm = 0.f;
     if (threadIdx.x < 256) {   // both lanes of the pair form d_h (lane 1 needs it for nothing; the arithmetic is uniform)
       const float prod = step > 0 ? gru_sum_split(red[0], g.sl, g.cc) : 0.f;
@@ -1437,7 +1386,7 @@ __global__ void __launch_bounds__(512) gru_seq_bwd(aslp_gru_seq a, SeqStatus st,
     __syncthreads();
     gru_store_split(red[1], gru_product<NB2>(a_lds, MP, bwb, k2, kw2 / 2, H, g), g);
     __syncthreads();
-    if (gru_failed(fail, 1)) return;
+    if (seq_failed(fail, 1)) return;
     float dg = 0.f, dzr = 0.f;
     if (threadIdx.x < 256) {
       dg = gru_sum_split(red[1], g.sl, g.cc);
@@ -1607,6 +1556,38 @@ static void note_launch(SeqRuntime &rt) {
   }
 }
 
+// The frame of one persistent launch, LSTM or GRU.  One at a time per process: the kernels share the placement table, the abort word and the share
+// ring, and two grids that both need every CU must not be half resident beside each other; launches from different host threads / streams are
+// chained by an event (no host wait).  The constructor, in this order: registers the thread as a grid-wide launcher (scratch.h: another thread's
+// grid-wide BatchNormalization / planes launches now stand down), takes the process's launch lock and (ASLP_DEVICE_SHARED=1 only) the device's,
+// held until the kernel has completed, chains behind the predecessor and takes the next epoch.  The destructor leaves the successor's marker and
+// reports a launch error before the locks go.
+struct PersistentLaunch {
+  struct Registered { Registered() { register_grid_wide_thread(); } } registered;   // the first member: runs before the lock is taken
+  SeqRuntime &rt;
+  const char *who;
+  std::lock_guard<std::mutex> launch_lock;
+  SharedDeviceLaunch shared_device;
+  PersistentLaunch(SeqRuntime &r, const char *w) : rt(r), who(w), launch_lock(r.launch_mu) {
+    chain_behind_last_launch(rt);
+    rt.epoch = (rt.epoch + 1u) & 0x0FFFFFFFu;   // 28 bits, never 0 (SeqStatus.epoch)
+    if (rt.epoch == 0u) rt.epoch = 1u;
+  }
+  // Device-side state is self-cleaning: the placement table is epoch-tagged and every share a backward launch publishes is consumed and reset inside
+  // that launch.  Only after a launch that gave up (the mapped error word moved), or when the caller says so, is the abort word put back by hand:
+  // true then, and the caller sees to the share ring.
+  bool abort_word_reset(bool anyway) {
+    if (*rt.host_err == rt.err_seen && !anyway) return false;
+    rt.err_seen = *rt.host_err;
+    ASLP_CHECK_HIP(hipMemsetAsync(rt.abort_flag, 0, 4, cur_stream()));
+    return true;
+  }
+  ~PersistentLaunch() {
+    note_launch(rt);
+    check_launch(who);
+  }
+};
+
 typedef void (*SeqKernel)(aslp_lstm_seq, SeqStatus, unsigned *);
 typedef void (*SeqKernelB)(aslp_lstm_seq, SeqStatus, unsigned *, float *);
 bool fast_act() {   // A/B switch: ASLP_LSTM_FAST_ACT=0 keeps the correctly rounded expf / division of the reference's CPU code
@@ -1763,25 +1744,11 @@ static void launch_seq(const aslp_lstm_seq *a, bool backward, const char *who) {
     }
   }
   SeqRuntime &rt = seq_runtime();
-  // One persistent launch at a time per process: the kernels share the placement table, the abort word and the share ring, and two
-  // grids that both need every CU must not be half resident beside each other.  Launches from different host threads / streams
-  // are therefore chained by an event (no host wait); the common single-stream case costs one event record per launch.
-  register_grid_wide_thread();   // (scratch.h: another thread's grid-wide BatchNormalization / planes launches now stand down)
-  std::lock_guard<std::mutex> launch_lock(rt.launch_mu);
-  SharedDeviceLaunch shared_device;   // ASLP_DEVICE_SHARED=1 only: cross-process lock held until this kernel has completed
-  chain_behind_last_launch(rt);
-  // Device-side state is self-cleaning: the placement table is epoch-tagged and every share a backward launch publishes is
-  // consumed and reset inside that launch.  Only after a launch that gave up (the mapped error word moved) are the abort
-  // word and the share ring put back by hand.
-  const size_t slot_bytes = sizeof(float) * (size_t)kMaxChains * kMaxWgPerChain * kMaxWgPerChain * 128;
-  if (*rt.host_err != rt.err_seen || !rt.ring_ready) {
-    rt.err_seen = *rt.host_err;
-    ASLP_CHECK_HIP(hipMemsetAsync(rt.abort_flag, 0, 4, cur_stream()));
-    ASLP_CHECK_HIP(hipMemsetAsync(rt.inbox, 0xFF, slot_bytes * kRing, cur_stream()));
+  PersistentLaunch launch(rt, who);
+  if (launch.abort_word_reset(!rt.ring_ready)) {   // the LSTM launch also refills the backward kernels' share ring
+    ASLP_CHECK_HIP(hipMemsetAsync(rt.inbox, 0xFF, sizeof(float) * (size_t)kRing * kMaxChains * kMaxWgPerChain * kMaxWgPerChain * 128, cur_stream()));
     rt.ring_ready = true;
   }
-  rt.epoch = (rt.epoch + 1u) & 0x0FFFFFFFu;
-  if (rt.epoch == 0u) rt.epoch = 1u;
   static const unsigned wave_collect = ((getenv("ASLP_LSTM_WAVE_COLLECT") != nullptr && getenv("ASLP_LSTM_WAVE_COLLECT")[0] == '0') ? 0u : 1u) |   // A/B switches
                                        ((getenv("ASLP_LSTM_READ_AHEAD") != nullptr && getenv("ASLP_LSTM_READ_AHEAD")[0] == '0') ? 0u : 2u);
   SeqStatus st = {rt.abort_flag, rt.host_err_dev, ((rt.timing_mode == 1 && !backward) || (rt.timing_mode == 2 && backward)) ? rt.timing : nullptr,
@@ -1794,8 +1761,6 @@ static void launch_seq(const aslp_lstm_seq *a, bool backward, const char *who) {
     if (split && a->s_count == 0 && (a->dmax_parts[0] || a->dmax_parts[1])) t_last_dmax = kMaxChains * wpc;
   }
   t_last_pieces = split ? np : 0;
-  note_launch(rt);
-  check_launch(who);
 }
 
 int aslp_gru_seq_supported(const aslp_gru_seq *a, int backward) {
@@ -1815,23 +1780,12 @@ static void launch_gru(const aslp_gru_seq *a, bool backward, const char *who) {
     return;
   }
   SeqRuntime &rt = seq_runtime();
-  register_grid_wide_thread();
-  std::lock_guard<std::mutex> launch_lock(rt.launch_mu);   // as launch_seq (the same lock: LSTM and GRU launches share the runtime state)
-  SharedDeviceLaunch shared_device;
-  chain_behind_last_launch(rt);
-  if (*rt.host_err != rt.err_seen) {
-    rt.err_seen = *rt.host_err;
-    rt.ring_ready = false;   // the LSTM backward's share ring may be half consumed: launch_seq puts it back
-    ASLP_CHECK_HIP(hipMemsetAsync(rt.abort_flag, 0, 4, cur_stream()));
-  }
-  rt.epoch = (rt.epoch + 1u) & 0x0FFFFFFFu;
-  if (rt.epoch == 0u) rt.epoch = 1u;
+  PersistentLaunch launch(rt, who);   // (the same lock as launch_seq: LSTM and GRU launches share the runtime state)
+  if (launch.abort_word_reset(false)) rt.ring_ready = false;   // the LSTM backward's share ring may be half consumed: launch_seq puts it back
   SeqStatus st = {rt.abort_flag, rt.host_err_dev, nullptr, ((rt.timing_mode == 3 && !backward) || (rt.timing_mode == 4 && backward)) ? rt.timing + 8 : nullptr,
                   rt.epoch, 0u};
   const int wpc = (a->H + kCellsPerWg - 1) / kCellsPerWg;
   hipLaunchKernelGGL(pick_gru(backward, a->H), dim3(kMaxChains * wpc), dim3(512), 0, cur_stream(), *a, st, rt.place);
-  note_launch(rt);
-  check_launch(who);
 }
 void aslp_gru_seq_forward(const aslp_gru_seq *a) { launch_gru(a, false, "aslp_gru_seq_forward"); }
 void aslp_gru_seq_backward(const aslp_gru_seq *a) { launch_gru(a, true, "aslp_gru_seq_backward"); }

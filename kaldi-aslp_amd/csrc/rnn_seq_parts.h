@@ -5,12 +5,17 @@
 //  * Parts of an LSTM timestep that the two kernels of a pass (fp32 product / fp16 product) instantiate from ONE copy here: forward the W_first
 //    staging and the r(0) staging, backward the gate-block derivatives.  Each takes scalars and pointers only, and with them the compiler's
 //    output for all 42 kernels is still identical to what the verbatim copies gave, instruction for instruction.
-// Three more pieces keep every kernel's resource table (SGPRs, VGPRs, AGPRs, scratch, spills, LDS, occupancy) as scalar-argument functions but
-// change the instruction text of the LSTM kernels -- the step-0 product (24 kernels), the grad_partial reduction (12; with the argument struct
-// by reference instead it moves counts) and reading the fail[] vote (36); all three together still keep the table.  They stay copies until
-// devtools/lstm_seq_sweep.py and a timing pair have been run for them on the GPU.  The other copies moved a resource count when taken out alone:
-// see the one-line notes at those places in rnn_persistent.hip.  Roles and the backward loads were only tried as records handed on by
-// reference, together with everything else (lstm_seq_bwd_h<true,1,1>: occupancy 5 -> 6); on their own they are open.
+//  * Two more, which keep every kernel's resource table (SGPRs, VGPRs, AGPRs, scratch, spills, LDS, occupancy: profiles/lstm_seq_parts_resources.txt)
+//    but change the instruction text of the LSTM kernels: reading the fail[] vote (seq_failed: all 36 LSTM kernels and, text unchanged, the GRU
+//    kernels) and the step-0 product (fwd_first_product, 24 kernels).  They take scalars, pointers and references to register arrays; aslp_lstm_seq,
+//    aslp_lstm_seq_dir or ChainRole handed on by reference move register counts.  Only the vote is on the per-timestep path.  Checked on the GPU
+//    against the copies: devtools/lstm_seq_sweep.py writes the same file (profiles/lstm_seq_sweep.txt, to cmp the next change against); the cfg3
+//    step is inside the old build's run-to-run distance in 9 of 9 (default path) and 6 of 9 (fp32 instruction) runs old / new / old (profiles/lstm_seq_parts_timing.txt).
+// What is still a copy in every kernel moved a resource count when taken out alone: see the one-line notes at those places in rnn_persistent.hip
+// (the hand-off waits, posting into fail[], the red[] store, the forward gate block, the backward stores and sums, the tail, and -- each tried on
+// its own as a function returning a small record -- the role / geometry prologue and the backward loads).  The grad_partial reduction behind the
+// backward loop keeps the table as a function but not the bits: the compiler then forms other FMAs in the time loop of lstm_seq_bwd
+// (note there; profiles/lstm_seq_grad_partial_as_function.txt).
 // This header defines a __shared__ array (g_tacc) and lives in an anonymous namespace: it is meant for ONE translation unit, rnn_persistent.hip.
 #pragma once
 #include "aslp_kernels.h"
@@ -108,6 +113,14 @@ __device__ __forceinline__ bool spin_ok(unsigned spins, long &t0, const SeqStatu
     __hip_atomic_fetch_add(st.host_err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
   }
   return false;
+}
+
+// The workgroup's vote behind a barrier: did one of its 8 waves give up in this round (spin_ok)?  Uniform: every wave reads the same eight words.
+__device__ __forceinline__ bool seq_failed(const int (*fail)[8], int round) {
+  int f = 0;
+#pragma unroll
+  for (int w = 0; w < 8; w++) f |= fail[round][w];
+  return f != 0;
 }
 
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
@@ -233,6 +246,25 @@ __device__ __forceinline__ void fwd_stage_r0(float (*m_lds)[MP], const float *y,
     const int sp = p / kq, k0 = 4 * (p % kq);
     *reinterpret_cast<f32x4 *>(&m_lds[sp][k0]) =
         *reinterpret_cast<const f32x4 *>(y + ((long)tp * S + min(s0 + sp, SE - 1)) * ld + col_first + k0);
+  }
+}
+// forward, step 0 with a W_first operand: r(0) W_first^T on v_mfma_f32_4x4x1, both operands from LDS (fwd_stage_r0, fwd_stage_w_first); this wave's
+// slice of K = k_first.  Result register r of a lane = stream 4 qs + r of tile column 32 h + 4 qc + jl, even / odd k in acc[h][0] / acc[h][1].
+template <int MP>
+__device__ __forceinline__ void fwd_first_product(f32x4 (&acc)[2][2], const float (*m_lds)[MP], const float (*wf_lds)[kFirstK + 4], int k_first, int wave, int qs,
+                                                  int qc, int jl) {
+  const int kwf = ((k_first + 31) / 32) * 4, kbf = wave * kwf;
+  const float *arow = &m_lds[4 * qs + jl][0];
+  for (int k0 = kbf; k0 < min(kbf + kwf, k_first); k0 += 4) {
+    const f32x4 av = *reinterpret_cast<const f32x4 *>(arow + k0);
+#pragma unroll
+    for (int h = 0; h < 2; h++) {
+      const f32x4 b = *reinterpret_cast<const f32x4 *>(&wf_lds[32 * h + 4 * qc + jl][k0]);
+      acc[h][0] = __builtin_amdgcn_mfma_f32_4x4x1f32(av.x, b.x, acc[h][0], 0, 0, 0);
+      acc[h][1] = __builtin_amdgcn_mfma_f32_4x4x1f32(av.y, b.y, acc[h][1], 0, 0, 0);
+      acc[h][0] = __builtin_amdgcn_mfma_f32_4x4x1f32(av.z, b.z, acc[h][0], 0, 0, 0);
+      acc[h][1] = __builtin_amdgcn_mfma_f32_4x4x1f32(av.w, b.w, acc[h][1], 0, 0, 0);
+    }
   }
 }
 
