@@ -459,7 +459,8 @@ static ctcStatus_t ctc_loss_impl(const float *const activations, int ld_acts, fl
   const int Tl = maxT > 0 ? maxT : 1;
   const size_t lds_lattice = sizeof(float) * 2 * maxS + sizeof(int) * maxS;
   const size_t lds_grad = sizeof(int) * 3 * maxS + sizeof(float) * kGradWaves * ((size_t)maxS + A);
-  if (lds_lattice > 160 * 1024 || lds_grad > 160 * 1024) return CTC_STATUS_INVALID_VALUE;  // alphabet + label length beyond one CU's LDS
+  // alphabet + label length beyond one CU's LDS; a scores-only call launches no gradient kernel and has no limit on the alphabet
+  if (lds_lattice > 160 * 1024 || (gradients != nullptr && lds_grad > 160 * 1024)) return CTC_STATUS_INVALID_VALUE;
   static bool attr_done = false;
   if (!attr_done) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(ctc_lattice_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
