@@ -456,6 +456,36 @@ typedef struct aslp_lstm_step_ {
 } aslp_lstm_step;
 void aslp_lstm_step_forward(const aslp_lstm_step *a);
 void aslp_lstm_step_backward(const aslp_lstm_step *a);
+/* Split-fp16 products on the per-timestep path (opt-in).  on = 1: aslp_lstm_step_forward_h / _backward_h below take their products
+ * m(t-1) W_eff^T and dGATES(next) W_eff on v_mfma_f32_32x32x16_f16 with operands as fp16 pieces; 0: off; -1 hands the choice to
+ * ASLP_LSTM_STEP_SPLIT_F16 (read once, "1" = on; default off).  Process-wide.  With the switch off nothing changes anywhere: the _h entry
+ * points run the fp32-instruction kernels of aslp_lstm_step_forward / _backward, bit for bit.  With it on the piece count is
+ * aslp_lstm_operand_pieces_get(): 2 = hi and lo' (fp32-equivalent operands), 1 = the hi piece alone.  ASLP_LSTM_SPLIT_F16 (the
+ * persistent kernels' switch) does not concern this path.  Not covered: the GRU step kernels, the unfused path, the step-0 W_first
+ * product.
+ * Numeric contract.  Weights: the caller hands in the planes of W_eff (forward) / W_eff^T (backward) in the format of csrc/split16.h
+ * (W s = hi + 2^-11 lo', s = 2^up from the bound in *w_slot; layout of the matrix, ldp halves per row, zeros in the padding), made once
+ * per training step (aslp_planes_convert, or the engine's PlaneSet::ConvertMany).  The kernels read 16 halves of k per step up to K
+ * rounded up to 16: they rely on ldp >= that (the planes' rows are padded to 64) and on the padding being zero; fp32 operand reads beyond
+ * K are replaced by zeros and never addressed.  Forward: m(t-1) is split as it is loaded, without a scale (|m| <= 1): hi = fp16(m), lo' =
+ * fp16((m - hi) 2^11).  Backward: dGATES(next) is split as it is loaded behind a power-of-two scale per stream row and run of up to 128
+ * consecutive k (one wave's K slice for C <= 1024; a longer slice is several runs, each unscaled into the fp32 sum before the next): the
+ * scale puts the run's largest finite |value| into [2^13, 2^14); an all-zero run takes scale 1 and contributes an exact zero.
+ * Two pieces: hi hi + 2^-11 (hi lo' + lo' hi) per k step, lo' lo' dropped (as the layer products); one piece: hi hi.  fp32 accumulation in
+ * k order per wave, the 4 waves' tiles added through LDS in wave order, the backward's 8 K-parts in part order: bit-reproducible.
+ * Everything outside the two products is the fp32 code of the entry points above. */
+typedef struct aslp_lstm_step_h_ {
+  aslp_lstm_step step;            /* as for aslp_lstm_step_forward / _backward (dir[d].w: the fp32 matrix the planes are of) */
+  const void *w_hi[2], *w_lo[2];  /* per direction: fp16 planes of dir[d].w, 16-byte aligned (w_lo is not read with one piece) */
+  const unsigned *w_slot[2];      /* per direction: device word, bits of the bound the planes are scaled by */
+  int ldp;                        /* halves per plane row: a multiple of 8, >= K rounded up to 16 (K = C forward, G*C backward) */
+} aslp_lstm_step_h;
+void aslp_lstm_step_split16(int on);
+int aslp_lstm_step_split16_get(void);   /* 1 / 0: what is in force */
+void aslp_lstm_step_forward_h(const aslp_lstm_step_h *a);
+void aslp_lstm_step_backward_h(const aslp_lstm_step_h *a);
+/* What the calling thread's latest aslp_lstm_step_forward(_h) / _backward(_h) multiplied with: 0 = the fp32 instruction, 1 / 2 = fp16 pieces. */
+int aslp_lstm_step_last_pieces(void);
 /* The same recurrence for a WHOLE sequence in one launch per pass (csrc/rnn_persistent.hip): the workgroups stay resident
  * for all T timesteps, the weights they multiply with live in registers, and m(t) / dGATES(t) travel between workgroups
  * through the buffers themselves (write-through stores, agent-scope loads, "not yet written" = the bit pattern 0xFFFFFFFF).
@@ -511,7 +541,8 @@ void aslp_lstm_split16(int on);
  * recurrent product is fp16(m(t-1)) (fp16(W sc) / sc)^T forward and fp16(dG s) / s times the hi piece of the W_eff rows backward, accumulated in
  * fp32 in a fixed order; everything outside the product stays fp32.  Any other n hands the choice back to ASLP_LSTM_PIECES (read once; "1"
  * selects one piece).  aslp_lstm_split16(0) / ASLP_LSTM_SPLIT_F16=0 wins: the fp32 instruction has no pieces.  Independent of
- * aslp_gemm_operand_planes.  The step-0 W_first product, the GRU kernels and the per-timestep path (csrc/rnn_fused.hip) are not affected. */
+ * aslp_gemm_operand_planes.  The step-0 W_first product and the GRU kernels are not affected; the per-timestep path (csrc/rnn_fused.hip)
+ * follows the piece count only under its own switch aslp_lstm_step_split16(1) (above), which aslp_lstm_split16(0) does not turn off. */
 void aslp_lstm_operand_pieces(int n);
 int aslp_lstm_operand_pieces_get(void);
 /* What the calling thread's latest aslp_lstm_seq_forward / _backward launched: 0 = the fp32 instruction, 1 / 2 = the fp16 kernels with that many

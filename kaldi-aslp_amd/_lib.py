@@ -53,6 +53,23 @@ class Seq(C.Structure):
                 ("dmax_parts", C.c_void_p * 2)]
 
 
+class StepDir(C.Structure):
+    """aslp_lstm_step_dir (include/aslp_kernels.h)"""
+    _fields_ = [("y_cur", C.c_void_p), ("y_prev", C.c_void_p), ("d_cur", C.c_void_p), ("d_next", C.c_void_p), ("y_next", C.c_void_p),
+                ("w", C.c_void_p), ("peep_i", C.c_void_p), ("peep_f", C.c_void_p), ("peep_o", C.c_void_p), ("seq_lengths", C.c_void_p),
+                ("t", C.c_int), ("has_next", C.c_int), ("no_product", C.c_int)]
+
+
+class Step(C.Structure):
+    """aslp_lstm_step (include/aslp_kernels.h)"""
+    _fields_ = [("dir", StepDir * 2), ("ndir", C.c_int), ("ld", C.c_int), ("ldw", C.c_int), ("S", C.c_int), ("C", C.c_int), ("cifg", C.c_int)]
+
+
+class StepH(C.Structure):
+    """aslp_lstm_step_h (include/aslp_kernels.h)"""
+    _fields_ = [("step", Step), ("w_hi", C.c_void_p * 2), ("w_lo", C.c_void_p * 2), ("w_slot", C.c_void_p * 2), ("ldp", C.c_int)]
+
+
 class RnnVecGrad(C.Structure):
     """aslp_rnn_vec_grad (include/aslp_kernels.h)"""
     _fields_ = [("d", C.c_void_p), ("x", C.c_void_p), ("ldx", C.c_int), ("n", C.c_int), ("corr", C.c_void_p), ("param", C.c_void_p)]
@@ -186,6 +203,13 @@ _sig("aslp_lstm_seq_forward", None, C.POINTER(Seq))
 _sig("aslp_lstm_seq_backward", None, C.POINTER(Seq))
 _sig("aslp_lstm_seq_last_dmax", _i)
 _sig("aslp_lstm_split16", None, _i)
+_sig("aslp_lstm_step_forward", None, C.POINTER(Step))
+_sig("aslp_lstm_step_backward", None, C.POINTER(Step))
+_sig("aslp_lstm_step_split16", None, _i)
+_sig("aslp_lstm_step_split16_get", _i)
+_sig("aslp_lstm_step_forward_h", None, C.POINTER(StepH))
+_sig("aslp_lstm_step_backward_h", None, C.POINTER(StepH))
+_sig("aslp_lstm_step_last_pieces", _i)
 _sig("aslp_region_profile", None, _i)
 _sig("aslp_region_reset", None)
 _sig("aslp_region_get", C.c_long, C.c_char_p, C.POINTER(C.c_double))

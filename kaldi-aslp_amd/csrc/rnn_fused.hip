@@ -14,6 +14,8 @@
 // W_eff's row slices are pinned to a workgroup index, hence to one XCD's L2, across the T launches.
 // Backward mirrors it:  d_m(t) = dm_ext(t) + dGATES(t+1) W_eff  (K = 4C, split over 4 workgroups x 4 waves,
 // partials to scratch) followed by the fused gate-block backward, which adds the partials in a fixed order.
+// Opt-in (aslp_lstm_step_split16): the same two products on v_mfma_f32_32x32x16_f16 with operands as fp16 pieces (lstm_step_fwd_h,
+// lstm_step_bwd_gemm_h; contract in include/aslp_kernels.h), everything around them unchanged.
 #include "aslp_kernels.h"
 #include "common.h"
 #include "scratch.h"
@@ -90,6 +92,124 @@ __global__ void __launch_bounds__(64 * kNW) lstm_step_fwd(aslp_lstm_step a) {
   ys[c] = g; ys[gf * C + c] = f; ys[go * C + c] = o; ys[oc + c] = cell; ys[oh + c] = hh; ys[om + c] = hh * o;
 }
 
+// ---- the fp16-piece kernels (aslp_lstm_step_split16).  They take lstm_step_fwd's prologue and gate block and lstm_step_bwd_gemm's reduction
+// as the functions below, statement for statement; the fp32-instruction kernels above keep their own text, so that the compiler's output
+// for them stays what it was (built from these functions lstm_step_fwd<false> came out with 32 instead of 34 SGPRs).
+// One thread's (stream, cell) of a forward step: its operands, requested before the product so their latency hides under it ...
+template <bool CIFG>
+struct StepFwdCell {
+  float *ys;
+  int sl, cc, c;
+  bool live, masked;
+  float xg, xf, xo, xi, cprev, pf, po, pi;
+};
+template <bool CIFG>
+__device__ __forceinline__ StepFwdCell<CIFG> step_fwd_cell_load(const aslp_lstm_step_dir &D, int C, int S, int ld, int s0, int c0) {
+  constexpr int G = CIFG ? 3 : 4;
+  constexpr int gi = 1, gf = CIFG ? 1 : 2, go = CIFG ? 2 : 3;
+  const int oc = G * C;
+  StepFwdCell<CIFG> e;
+  e.sl = threadIdx.x / kCB; e.cc = threadIdx.x % kCB;
+  const int s = s0 + e.sl;
+  e.c = c0 + e.cc;
+  e.live = threadIdx.x < 256 && s < S && e.c < C;  // the first 4 waves finish the 256 (stream, cell) pairs
+  e.ys = D.y_cur + (long)(e.live ? s : 0) * ld;
+  const int cq = e.live ? e.c : 0;
+  e.xg = e.ys[cq]; e.xf = e.ys[gf * C + cq]; e.xo = e.ys[go * C + cq]; e.xi = CIFG ? 0.f : e.ys[gi * C + cq];
+  e.cprev = D.y_prev[(long)(e.live ? s : 0) * ld + oc + cq];
+  e.pf = D.peep_f[cq]; e.po = D.peep_o[cq]; e.pi = CIFG ? 0.f : D.peep_i[cq];
+  e.masked = D.seq_lengths && D.t > D.seq_lengths[e.live ? s : 0];
+  return e;
+}
+// ... and the gate block on the 4 waves' partial tiles, added in wave order (call after the barrier)
+template <bool CIFG>
+__device__ __forceinline__ void step_fwd_cell_finish(const StepFwdCell<CIFG> &e, const float (*red)[32 * kPad], int C) {
+  constexpr int G = CIFG ? 3 : 4;
+  constexpr int gi = 1, gf = CIFG ? 1 : 2, go = CIFG ? 2 : 3;
+  const int GC = G * C, oc = GC, oh = GC + C, om = GC + 2 * C;
+  if (!e.live) return;
+  float *ys = e.ys;
+  const int c = e.c;
+  float pre[G];
+#pragma unroll
+  for (int g = 0; g < G; g++) {
+    const int n = g * kCB + e.cc;
+    float acc = red[0][e.sl * kPad + n];
+#pragma unroll
+    for (int w = 1; w < kNW; w++) acc += red[w][e.sl * kPad + n];
+    pre[g] = acc;
+  }
+  if (e.masked) {  // nnet-blstm-projected-streams.h:654-657
+    ys[c] = 0.f; ys[gf * C + c] = 0.f; ys[go * C + c] = 0.f; ys[oc + c] = 0.f; ys[oh + c] = 0.f; ys[om + c] = 0.f;
+    if (!CIFG) ys[gi * C + c] = 0.f;
+    return;
+  }
+  const float g = tanh_ref(e.xg + pre[0]);
+  const float f = sigmoid_ref(e.xf + pre[gf] + e.cprev * e.pf);
+  float cell;
+  if (!CIFG) {
+    const float i = sigmoid_ref(e.xi + pre[gi] + e.cprev * e.pi);
+    ys[gi * C + c] = i;
+    cell = g * i + e.cprev * f;
+  } else {
+    cell = -g * f + g + e.cprev * f;
+  }
+  cell = fminf(fmaxf(cell, -50.0f), 50.0f);
+  const float hh = tanh_ref(cell);
+  const float o = sigmoid_ref(e.xo + pre[go] + cell * e.po);
+  ys[c] = g; ys[gf * C + c] = f; ys[go * C + c] = o; ys[oc + c] = cell; ys[oh + c] = hh; ys[om + c] = hh * o;
+}
+
+// the 4 waves' partial tiles, added in wave order, to partial[slab][s][c] (slab = direction x K-part)
+__device__ __forceinline__ void step_bwd_store_partial(const float (*red)[32 * kPad], float *__restrict__ partial, int slab, int S, int C, int s0, int c0) {
+  float *out = partial + ((long)slab * S) * C;
+  for (int e = threadIdx.x; e < 32 * 32; e += 64 * kNW) {
+    const int sl = e >> 5, n = e & 31;
+    if (s0 + sl < S && c0 + n < C) {
+      float acc = red[0][sl * kPad + n];
+#pragma unroll
+      for (int w = 1; w < kNW; w++) acc += red[w][sl * kPad + n];
+      out[(long)(s0 + sl) * C + c0 + n] = acc;
+    }
+  }
+}
+
+// The same step with the product on v_mfma_f32_32x32x16_f16 (aslp_lstm_step_split16): m(t-1) split into NP fp16 pieces as it is loaded
+// (|m| <= 1: no scale), W_eff from its planes (a.w_hi / w_lo, scaled by the bound in *a.w_slot); same grid, same K split over the 4
+// waves (contiguous runs of 16-wide k steps), same reduction and gate block.  The k tail (C % 16) reads the planes' zero padding and
+// zeros for m; rows of invalid (gate, cell) / stream pairs read row 0 / the last stream and their outputs are not stored.
+constexpr int kStepHU = 8;   // 16-wide k steps in flight per wave
+template <bool CIFG, int NP>
+__global__ void __launch_bounds__(64 * kNW) lstm_step_fwd_h(aslp_lstm_step_h ah) {
+  __shared__ float red[kNW][32 * kPad];
+  constexpr int G = CIFG ? 3 : 4;
+  const aslp_lstm_step_dir D = ah.step.dir[blockIdx.z];
+  const int C = ah.step.C, S = ah.step.S, ld = ah.step.ld;
+  const int om = G * C + 2 * C;
+  const int c0 = blockIdx.x * kCB, s0 = blockIdx.y * 32;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, l31 = lane & 31, h = lane >> 5;
+  const StepFwdCell<CIFG> e = step_fwd_cell_load<CIFG>(D, C, S, ld, s0, c0);
+  {
+    const int srow = min(s0 + l31, S - 1);
+    const int gate = l31 / kCB, cell = c0 + (l31 % kCB);
+    const bool nvalid = gate < G && cell < C;
+    const float *arow = D.y_prev + (long)srow * ld + om;
+    const long boff = (long)(nvalid ? gate * C + cell : 0) * ah.ldp;
+    const h16 *bhi = static_cast<const h16 *>(ah.w_hi[blockIdx.z]) + boff;
+    const h16 *blo = NP == 2 ? static_cast<const h16 *>(ah.w_lo[blockIdx.z]) + boff : bhi;
+    const float inv_w = ldexpf(1.0f, -s16_exponent(*ah.w_slot[blockIdx.z]));
+    f32x16 acc = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, acx = acc;
+    const int nst = (C + 15) / 16, per = (nst + kNW - 1) / kNW, qend = min(nst, (wave + 1) * per);
+    if (!D.no_product)
+      for (int q0 = wave * per; q0 < qend; q0 += kStepHU) mfma_run_h<NP, kStepHU, false, false>(acc, acx, arow, C, bhi, blo, q0, qend, h, nullptr);
+    if (NP == 2) acc += acx * (1.0f / 2048.f);
+    acc *= inv_w;
+    store_tile(red[wave], acc, lane);
+  }
+  __syncthreads();
+  step_fwd_cell_finish<CIFG>(e, red, C);
+}
+
 // partial[dir][kq][s][c] = sum over this workgroup's K-quarter of dGATES(next)[s][k] * W_eff^T[c][k]
 template <int G>
 __global__ void __launch_bounds__(64 * kNW) lstm_step_bwd_gemm(aslp_lstm_step a, float *__restrict__ partial) {
@@ -117,6 +237,41 @@ __global__ void __launch_bounds__(64 * kNW) lstm_step_bwd_gemm(aslp_lstm_step a,
       out[(long)(s0 + sl) * C + c0 + n] = acc;
     }
   }
+}
+
+// The same partial products on v_mfma_f32_32x32x16_f16 (aslp_lstm_step_split16).  The tile is taken transposed -- W_eff^T rows (from their
+// planes) as the A operand, dGATES(next) as B -- so that a stream is a lane's COLUMN of the accumulator: dGATES sits behind a power-of-two
+// scale per stream row and run of kStepHU k steps (128 consecutive k; one wave's K slice for C <= 1024), formed from the run's largest
+// finite |value| as it is loaded, and each lane unscales its own column before the run is added to the wave's fp32 sum.  An all-zero run
+// takes scale 1 and adds an exact zero.  Same grid, K split (contiguous runs per part = K-part x wave) and reduction as lstm_step_bwd_gemm.
+template <int G, int NP>
+__global__ void __launch_bounds__(64 * kNW) lstm_step_bwd_gemm_h(aslp_lstm_step_h ah, float *__restrict__ partial) {
+  __shared__ float red[kNW][32 * kPad];
+  const aslp_lstm_step_dir D = ah.step.dir[blockIdx.z];
+  const int C = ah.step.C, S = ah.step.S, ld = ah.step.ld, GC = G * C;
+  const int c0 = blockIdx.x * 32, kq = blockIdx.y % kKQ, s0 = (blockIdx.y / kKQ) * 32;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, l31 = lane & 31, h = lane >> 5;
+  {
+    const float *drow = D.d_next + (long)min(s0 + l31, S - 1) * ld;          // dGATES(next), columns [0, GC)
+    const long woff = (long)min(c0 + l31, C - 1) * ah.ldp;                  // W_eff^T row of cell c0 + l31
+    const h16 *whi = static_cast<const h16 *>(ah.w_hi[blockIdx.z]) + woff;
+    const h16 *wlo = NP == 2 ? static_cast<const h16 *>(ah.w_lo[blockIdx.z]) + woff : whi;
+    const float inv_w = ldexpf(1.0f, -s16_exponent(*ah.w_slot[blockIdx.z]));
+    const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    f32x16 tot = zero;
+    const int nst = (GC + 15) / 16, per = (nst + kNW * kKQ - 1) / (kNW * kKQ), part = kq * kNW + wave, qend = min(nst, (part + 1) * per);
+    for (int q0 = part * per; q0 < qend; q0 += kStepHU) {
+      f32x16 acc = zero, acx = zero;
+      float inv_s = 1.0f;
+      mfma_run_h<NP, kStepHU, true, true>(acc, acx, drow, GC, whi, wlo, q0, qend, h, &inv_s);
+      if (NP == 2) acc += acx * (1.0f / 2048.f);
+      tot += acc * inv_s;
+    }
+    tot *= inv_w;
+    store_tile_t(red[wave], tot, lane);
+  }
+  __syncthreads();
+  step_bwd_store_partial(red, partial, blockIdx.z * kKQ + kq, S, C, s0, c0);
 }
 
 // gate-block backward of step t for every direction; d_m = dm_ext (already in the m column) + the K-split partials
@@ -179,6 +334,37 @@ bool step_args_ok(const aslp_lstm_step *a, const char *who) {
   return true;
 }
 
+// the planes a split-fp16 step launch reads: K (= C forward, G C backward) rounded up to 16 halves per row must lie inside a plane row
+bool step_planes_ok(const aslp_lstm_step_h *a, int K, int np, const char *who) {
+  bool ok = (a->ldp & 7) == 0 && a->ldp >= (K + 15) / 16 * 16;
+  for (int d = 0; ok && d < a->step.ndir; d++)
+    ok = a->w_hi[d] != nullptr && aligned16(a->w_hi[d]) && a->w_slot[d] != nullptr && (np == 1 || (a->w_lo[d] != nullptr && aligned16(a->w_lo[d])));
+  if (!ok) set_error(std::string(who) + ": bad planes (needs hi / lo / slot per direction, 16-byte aligned, ldp a multiple of 8 and >= K rounded up to 16)");
+  return ok;
+}
+
+// split-fp16 products on this path: opt-in (aslp_lstm_step_split16 / ASLP_LSTM_STEP_SPLIT_F16=1)
+int g_step_split_override = -1;   // -1 = the environment decides
+bool step_split_on() {
+  static const bool env = getenv("ASLP_LSTM_STEP_SPLIT_F16") != nullptr && getenv("ASLP_LSTM_STEP_SPLIT_F16")[0] == '1' && getenv("ASLP_LSTM_STEP_SPLIT_F16")[1] == 0;
+  return g_step_split_override >= 0 ? g_step_split_override != 0 : env;
+}
+thread_local int t_step_last_pieces = 0;   // aslp_lstm_step_last_pieces()
+
+void step_backward_cell(const aslp_lstm_step *a, const float *partial, int with_partial, const char *who) {
+  dim3 grid(grid_for((long)a->S * a->C), a->ndir);
+  if (a->cifg) hipLaunchKernelGGL((lstm_step_bwd_cell<true>), grid, dim3(kBlock), 0, cur_stream(), *a, partial, with_partial);
+  else hipLaunchKernelGGL((lstm_step_bwd_cell<false>), grid, dim3(kBlock), 0, cur_stream(), *a, partial, with_partial);
+  check_launch(who);
+}
+// scratch for the backward's K-split partial products (NULL with *with_partial set: the allocation failed)
+float *step_partial_scratch(const aslp_lstm_step *a, int *with_partial) {
+  *with_partial = 0;
+  for (int d = 0; d < a->ndir; d++) *with_partial |= a->dir[d].has_next;
+  if (!*with_partial) return nullptr;
+  return static_cast<float *>(scratch(kScratchMisc, sizeof(float) * (size_t)a->ndir * kKQ * a->S * a->C));
+}
+
 }  // namespace
 }  // namespace aslp
 
@@ -186,8 +372,13 @@ using namespace aslp;
 
 extern "C" {
 
+void aslp_lstm_step_split16(int on) { g_step_split_override = on < 0 ? -1 : (on != 0); }
+int aslp_lstm_step_split16_get(void) { return step_split_on() ? 1 : 0; }
+int aslp_lstm_step_last_pieces(void) { return t_step_last_pieces; }
+
 void aslp_lstm_step_forward(const aslp_lstm_step *a) {
   if (!step_args_ok(a, "aslp_lstm_step_forward")) return;
+  t_step_last_pieces = 0;
   dim3 grid((a->C + kCB - 1) / kCB, (a->S + 31) / 32, a->ndir);
   if (a->cifg) hipLaunchKernelGGL((lstm_step_fwd<true>), grid, dim3(64 * kNW), 0, cur_stream(), *a);
   else hipLaunchKernelGGL((lstm_step_fwd<false>), grid, dim3(64 * kNW), 0, cur_stream(), *a);
@@ -196,20 +387,57 @@ void aslp_lstm_step_forward(const aslp_lstm_step *a) {
 
 void aslp_lstm_step_backward(const aslp_lstm_step *a) {
   if (!step_args_ok(a, "aslp_lstm_step_backward")) return;
+  t_step_last_pieces = 0;
   int with_partial = 0;
-  for (int d = 0; d < a->ndir; d++) with_partial |= a->dir[d].has_next;
-  float *partial = nullptr;
+  float *partial = step_partial_scratch(a, &with_partial);
   if (with_partial) {
-    partial = static_cast<float *>(scratch(kScratchMisc, sizeof(float) * (size_t)a->ndir * kKQ * a->S * a->C));
     if (!partial) return;
     dim3 grid((a->C + 31) / 32, kKQ * ((a->S + 31) / 32), a->ndir);
     if (a->cifg) hipLaunchKernelGGL((lstm_step_bwd_gemm<3>), grid, dim3(64 * kNW), 0, cur_stream(), *a, partial);
     else hipLaunchKernelGGL((lstm_step_bwd_gemm<4>), grid, dim3(64 * kNW), 0, cur_stream(), *a, partial);
   }
-  dim3 grid(grid_for((long)a->S * a->C), a->ndir);
-  if (a->cifg) hipLaunchKernelGGL((lstm_step_bwd_cell<true>), grid, dim3(kBlock), 0, cur_stream(), *a, partial, with_partial);
-  else hipLaunchKernelGGL((lstm_step_bwd_cell<false>), grid, dim3(kBlock), 0, cur_stream(), *a, partial, with_partial);
-  check_launch("aslp_lstm_step_backward");
+  step_backward_cell(a, partial, with_partial, "aslp_lstm_step_backward");
+}
+
+void aslp_lstm_step_forward_h(const aslp_lstm_step_h *ah) {
+  if (!ah) { set_error("aslp_lstm_step_forward_h: bad arguments"); return; }
+  if (!step_split_on()) { aslp_lstm_step_forward(&ah->step); return; }
+  const aslp_lstm_step *a = &ah->step;
+  const int np = aslp_lstm_operand_pieces_get() == 1 ? 1 : 2;
+  if (!step_args_ok(a, "aslp_lstm_step_forward_h") || !step_planes_ok(ah, a->C, np, "aslp_lstm_step_forward_h")) return;
+  t_step_last_pieces = np;
+  dim3 grid((a->C + kCB - 1) / kCB, (a->S + 31) / 32, a->ndir), block(64 * kNW);
+  if (a->cifg) {
+    if (np == 1) hipLaunchKernelGGL((lstm_step_fwd_h<true, 1>), grid, block, 0, cur_stream(), *ah);
+    else hipLaunchKernelGGL((lstm_step_fwd_h<true, 2>), grid, block, 0, cur_stream(), *ah);
+  } else {
+    if (np == 1) hipLaunchKernelGGL((lstm_step_fwd_h<false, 1>), grid, block, 0, cur_stream(), *ah);
+    else hipLaunchKernelGGL((lstm_step_fwd_h<false, 2>), grid, block, 0, cur_stream(), *ah);
+  }
+  check_launch("aslp_lstm_step_forward_h");
+}
+
+void aslp_lstm_step_backward_h(const aslp_lstm_step_h *ah) {
+  if (!ah) { set_error("aslp_lstm_step_backward_h: bad arguments"); return; }
+  if (!step_split_on()) { aslp_lstm_step_backward(&ah->step); return; }
+  const aslp_lstm_step *a = &ah->step;
+  const int np = aslp_lstm_operand_pieces_get() == 1 ? 1 : 2;
+  if (!step_args_ok(a, "aslp_lstm_step_backward_h")) return;
+  int with_partial = 0;
+  float *partial = step_partial_scratch(a, &with_partial);
+  t_step_last_pieces = np;
+  if (with_partial) {
+    if (!partial || !step_planes_ok(ah, (a->cifg ? 3 : 4) * a->C, np, "aslp_lstm_step_backward_h")) return;
+    dim3 grid((a->C + 31) / 32, kKQ * ((a->S + 31) / 32), a->ndir), block(64 * kNW);
+    if (a->cifg) {
+      if (np == 1) hipLaunchKernelGGL((lstm_step_bwd_gemm_h<3, 1>), grid, block, 0, cur_stream(), *ah, partial);
+      else hipLaunchKernelGGL((lstm_step_bwd_gemm_h<3, 2>), grid, block, 0, cur_stream(), *ah, partial);
+    } else {
+      if (np == 1) hipLaunchKernelGGL((lstm_step_bwd_gemm_h<4, 1>), grid, block, 0, cur_stream(), *ah, partial);
+      else hipLaunchKernelGGL((lstm_step_bwd_gemm_h<4, 2>), grid, block, 0, cur_stream(), *ah, partial);
+    }
+  }
+  step_backward_cell(a, partial, with_partial, "aslp_lstm_step_backward_h");
 }
 
 }  // extern "C"

@@ -238,6 +238,7 @@ void LstmDir::RefreshEff() const {
   }
   eff_dirty = false;
   eff_t_dirty = true;
+  step_planes.Invalidate(true, true);
 }
 // W_eff^T: only the one-launch-per-timestep backward path multiplies with it (the persistent kernel takes rows of W_eff)
 void LstmDir::RefreshEffT() const {
@@ -249,6 +250,25 @@ void LstmDir::RefreshEffT() const {
     w_eff_t.CopyFromMatTrans(w_r);
   }
   eff_t_dirty = false;
+  step_planes.Invalidate(false, true);
+}
+// The planes travel with the fp32 matrices' own flags: RefreshEff / RefreshEffPair (every path on which Weff() changes or is marked stale
+// runs through eff_dirty and so through them) and RefreshEffT drop them above, so planes marked ok here are planes of the current matrix.
+bool LstmDir::RefreshStepPlanes(const LstmDir *const *dirs, int n, bool transposed) {
+  PlaneSet::ConvertSpec sp[2];
+  bool *made[2];
+  int m = 0;
+  for (int d = 0; d < n && d < 2; d++) {
+    LstmStepPlanes *pl = dirs[d]->step_planes.get();
+    bool &ok = transposed ? pl->eff_t_ok : pl->eff_ok;
+    if (ok) continue;
+    const CuMatrixBase &w = transposed ? static_cast<const CuMatrixBase &>(dirs[d]->w_eff_t) : dirs[d]->Weff();
+    sp[m] = PlaneSet::ConvertSpec{transposed ? &pl->eff_t : &pl->eff, w.Data(), w.NumRows(), w.NumCols(), w.Stride()};
+    made[m++] = &ok;
+  }
+  if (m > 0 && !PlaneSet::ConvertMany(sp, m)) return false;
+  for (int i = 0; i < m; i++) *made[i] = true;
+  return true;
 }
 
 void LstmDir::ForwardPrepare(const CuMatrixBase &in, int T, int S, bool reverse, const CuMatrixBase *init_state, CuMatrix *buf,
@@ -354,6 +374,8 @@ void LstmDir::RefreshEffPair(const LstmDir &f, const LstmDir &b, const S16View *
   AddMatMatPair(f.w_eff, b.w_eff, 1.0, f.w_r, b.w_r, kNoTrans, f.w_rm, b.w_rm, kNoTrans, 0.0, nullptr, nullptr, views);
   f.eff_dirty = b.eff_dirty = false;
   f.eff_t_dirty = b.eff_t_dirty = true;
+  f.step_planes.Invalidate(true, true);
+  b.step_planes.Invalidate(true, true);
 }
 
 void LstmDir::ForwardPreparePair(const LstmDir &f, const LstmDir &b, const CuMatrixBase &in, int T, int S, const CuMatrixBase *init_f,
@@ -773,13 +795,23 @@ void LstmFamily::PropagateFnc(const CuMatrixBase &in, CuMatrixBase *out) {
         a.dir[d].peep_o = p.peep_o.Data();
         a.dir[d].seq_lengths = (d == 1 && !cfg_.lc) ? seq_len_dev_.Data() : nullptr;
       }
+      // opt-in (aslp_lstm_step_split16): the product on the fp16 instruction from the planes of W_eff, made once per step
+      aslp_lstm_step_h ah = aslp_lstm_step_h();
+      const LstmDir *dirs[2] = {&f_, &b_};
+      const bool split = aslp_lstm_step_split16_get() != 0 && LstmDir::RefreshStepPlanes(dirs, a.ndir, false);
+      for (int d = 0; split && d < a.ndir; d++) {
+        const S16View v = dirs[d]->step_planes.get()->eff.View();
+        ASLP_ASSERT(d == 0 || v.ld == ah.ldp);
+        ah.w_hi[d] = v.hi; ah.w_lo[d] = v.lo; ah.w_slot[d] = v.slot; ah.ldp = v.ld;
+      }
       RegionScope timed("lstm_recurrence_fwd");
       for (int step = 0; step < T; step++) {
         const int tf = 1 + step, tb = T - step;
         a.dir[0].no_product = (step == 0 && carried && cfg_.proj) ? 1 : 0;
         a.dir[0].y_cur = f_buf_.RowData(tf * S); a.dir[0].y_prev = f_buf_.RowData((tf - 1) * S); a.dir[0].t = tf;
         if (cfg_.bidir) { a.dir[1].y_cur = b_buf_.RowData(tb * S); a.dir[1].y_prev = b_buf_.RowData((tb + 1) * S); a.dir[1].t = tb; }
-        aslp_lstm_step_forward(&a);
+        if (split) { ah.step = a; aslp_lstm_step_forward_h(&ah); }
+        else aslp_lstm_step_forward(&a);
       }
     }
     CheckK();
@@ -877,6 +909,14 @@ void LstmFamily::BackpropagateFnc(const CuMatrixBase &in, const CuMatrixBase &, 
         a.dir[d].peep_f = p.peep_f.Data();
         a.dir[d].peep_o = p.peep_o.Data();
       }
+      aslp_lstm_step_h ah = aslp_lstm_step_h();   // as in PropagateFnc, with the planes of W_eff^T
+      const LstmDir *dirs[2] = {&f_, &b_};
+      const bool split = aslp_lstm_step_split16_get() != 0 && LstmDir::RefreshStepPlanes(dirs, a.ndir, true);
+      for (int d = 0; split && d < a.ndir; d++) {
+        const S16View v = dirs[d]->step_planes.get()->eff_t.View();
+        ASLP_ASSERT(d == 0 || v.ld == ah.ldp);
+        ah.w_hi[d] = v.hi; ah.w_lo[d] = v.lo; ah.w_slot[d] = v.slot; ah.ldp = v.ld;
+      }
       RegionScope timed("lstm_recurrence_bwd");
       for (int step = 0; step < T; step++) {
         const int tf = T - step, tb = 1 + step;  // BPTT runs against each direction's recursion
@@ -888,7 +928,8 @@ void LstmFamily::BackpropagateFnc(const CuMatrixBase &in, const CuMatrixBase &, 
           a.dir[1].y_cur = b_buf_.RowData(tb * S); a.dir[1].y_next = b_buf_.RowData((tb - 1) * S); a.dir[1].y_prev = b_buf_.RowData((tb + 1) * S);
           a.dir[1].has_next = step > 0;
         }
-        aslp_lstm_step_backward(&a);
+        if (split) { ah.step = a; aslp_lstm_step_backward_h(&ah); }
+        else aslp_lstm_step_backward(&a);
       }
     }
     CheckK();

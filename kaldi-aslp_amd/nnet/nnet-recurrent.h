@@ -61,6 +61,21 @@ class RecurrentBase : public UpdatableComponent {
   bool in_diff_unused_ = false, grads_aside_ = false;
 };
 
+// fp16 planes (csrc/split16.h) of W_eff and W_eff^T for the split-fp16 products of the per-timestep path (aslp_lstm_step_split16): made
+// once per training step, valid exactly as long as the fp32 matrices they are of (LstmDir::eff_dirty / eff_t_dirty below)
+struct LstmStepPlanes {
+  PlaneSet eff, eff_t;
+  bool eff_ok = false, eff_t_ok = false;
+};
+struct LstmStepPlanesHolder {   // a copied direction starts without planes
+  LstmStepPlanesHolder() = default;
+  LstmStepPlanesHolder(const LstmStepPlanesHolder &) {}
+  LstmStepPlanesHolder &operator=(const LstmStepPlanesHolder &) { return *this; }
+  LstmStepPlanes *get() { if (!p) p.reset(new LstmStepPlanes()); return p.get(); }
+  void Invalidate(bool eff, bool eff_t) { if (p) { if (eff) p->eff_ok = false; if (eff_t) p->eff_t_ok = false; } }
+  std::unique_ptr<LstmStepPlanes> p;
+};
+
 struct LstmDir {
   int D = 0, C = 0, R = 0;  // input dim, cells, projection dim (0: none)
   bool cifg = false;
@@ -69,6 +84,7 @@ struct LstmDir {
   // of the fused recurrence (csrc/rnn_fused.hip); refreshed lazily after every parameter change
   mutable CuMatrix w_eff, w_eff_t;
   mutable bool eff_dirty = true, eff_t_dirty = true;
+  mutable LstmStepPlanesHolder step_planes;   // planes of Weff() / w_eff_t: invalidated wherever those are re-made or marked stale
   bool aliased = false;  // GetGpuParams handed the tensors out (model sync may rewrite them at any time)
   CuVector bias, peep_i, peep_f, peep_o, bias_corr, peep_i_corr, peep_f_corr, peep_o_corr;
 
@@ -117,6 +133,9 @@ struct LstmDir {
   bool FusedOk() const;  // C % 4 == 0 (16-byte operand loads) and not disabled by ASLP_LSTM_UNFUSED=1 (A/B switch for tests)
   void RefreshEff() const;
   void RefreshEffT() const;
+  // planes of Weff() (transposed = false) or w_eff_t (true) of n <= 2 directions, whose fp32 matrices are up to date: one conversion for
+  // those that are stale.  false: not made (the caller keeps the fp32-instruction kernels)
+  static bool RefreshStepPlanes(const LstmDir *const *dirs, int n, bool transposed);
   // Both directions of a bidirectional layer: every batched product below exists twice with the same shape, and most of them
   // (K or N = R, or a [R x C] output) cannot fill the chip alone -- they go out as pairs, one launch each (AddMatMatPair).
   // `with_gemm = false` on the single-direction methods leaves out the product the *Pair function then issues for both.

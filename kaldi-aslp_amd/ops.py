@@ -85,6 +85,24 @@ def lstm_operand_pieces(n):
         lib.aslp_lstm_operand_pieces(before)
 
 
+def set_lstm_step_split16(on):
+    """split-fp16 products on the per-timestep LSTM path (aslp_lstm_step_split16): 1 = the step kernels multiply on the fp16 instruction with
+    lstm_operand_pieces pieces per operand, 0 = the fp32 instruction (default), -1 = what ASLP_LSTM_STEP_SPLIT_F16 said"""
+    lib.aslp_lstm_step_split16(int(on))
+
+
+@contextlib.contextmanager
+def lstm_step_split16(on):
+    """per-timestep LSTM recurrences inside the block run with the switch at `on`; the setting in force before comes back on exit (pinned as an
+    explicit setting, as lstm_operand_pieces does; set_lstm_step_split16(-1) hands the choice back to the environment)"""
+    before = lib.aslp_lstm_step_split16_get()
+    lib.aslp_lstm_step_split16(int(on))
+    try:
+        yield
+    finally:
+        lib.aslp_lstm_step_split16(before)
+
+
 class Planes:
     """the two fp16 planes of an fp32 matrix (aslp_planes_*): made once, read by every product the matrix takes part in"""
 
