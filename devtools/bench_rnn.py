@@ -1,5 +1,5 @@
 """One-layer recurrent components (SURVEY 8d cfg5 swaps) at S streams x T frames: train-step time through the engine.
-Usage: python devtools/bench_rnn.py [S] [T]"""
+Usage: python devtools/bench_rnn.py [S] [T] [component name: only that one]"""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -16,7 +16,10 @@ cases = [("GruStreams", "<GruStreams> <InputDim> 512 <OutputDim> 512 <ParamScale
          ("BLstmProjectedStreams", "<BLstmProjectedStreams> <InputDim> 512 <OutputDim> 512 <CellDim> 512 <ParamScale> 0.02 <ClipGradient> 5.0", 512),
          ("Lstm", "<Lstm> <InputDim> 512 <OutputDim> 512 <ParamScale> 0.01 <ClipGradient> 5.0", 512),
          ("BLstm", "<BLstm> <InputDim> 512 <OutputDim> 1024 <ParamScale> 0.01 <ClipGradient> 5.0", 1024)]
+only = sys.argv[3] if len(sys.argv) > 3 else None
 for name, line, od in cases:
+    if only and name != only:
+        continue
     proto = "<NnetProto>\n%s\n<AffineTransform> <InputDim> %d <OutputDim> %d <BiasMean> 0.0 <BiasRange> 0.0 <ParamStddev> 0.04\n<Softmax> <InputDim> %d <OutputDim> %d\n</NnetProto>\n" % (line, od, A, A, A)
     net = aslp.Nnet.Init(proto, seed=1)
     net.SetTrainOptions(learn_rate=1e-5, momentum=0.9)

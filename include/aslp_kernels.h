@@ -595,6 +595,19 @@ typedef struct aslp_gru_seq_ {
 int aslp_gru_seq_supported(const aslp_gru_seq *a, int backward);
 void aslp_gru_seq_forward(const aslp_gru_seq *a);
 void aslp_gru_seq_backward(const aslp_gru_seq *a);
+/* fp16 pieces per operand of the four recurrent products inside aslp_gru_seq_forward / _backward.  0 (default): the fp32 instruction
+ * v_mfma_f32_4x4x1 (gru_seq_fwd / gru_seq_bwd).  1 / 2 (opt-in): v_mfma_f32_16x16x32_f16 (gru_seq_fwd_h / gru_seq_bwd_h) with that many pieces --
+ * 2: every operand as hi and lo', fp32-equivalent; 1: the hi piece alone, i.e. fp16(x s) / s times fp16(W sc) / sc accumulated in fp32 in a fixed
+ * order, s a power of two per stream and K slice of a wave, sc one per output column, so no magnitude of h(0), [d_z | d_r] or d_m is excluded.
+ * The weights still arrive as fp32 matrices; everything outside the products stays fp32.  Any other n hands the choice to ASLP_GRU_SEQ_PIECES
+ * (read once; "0", "1", "2"; unset or anything else counts as 0).  Independent of aslp_lstm_operand_pieces, aslp_lstm_split16,
+ * aslp_lstm_step_split16 and aslp_gemm_operand_planes, none of which reaches the GRU kernels; aslp_gru_step_* (csrc/gru_fused.hip) and the unfused
+ * path are not affected.  aslp_gru_seq_supported probes the kernel the setting selects. */
+void aslp_gru_seq_pieces(int n);
+int aslp_gru_seq_pieces_get(void);
+/* What the calling thread's latest aslp_gru_seq_forward / _backward launched: 0 = the fp32 instruction, 1 / 2 = the fp16 kernels with that many
+ * pieces per operand.  Read-only, like aslp_lstm_seq_last_pieces(). */
+int aslp_gru_seq_last_pieces(void);
 /* GruStreams (nnet-gru-streams.h:275-303, 344-383), columns [z|r|m|g|h] */
 /* GRU recurrence, one timestep, both dependent products fused with their gate arithmetic (csrc/gru_fused.hip):
  * forward = aslp_gru_forward1/2 with the two skinny GEMMs folded in; backward likewise, reading TRANSPOSED copies of the

@@ -184,6 +184,9 @@ _sig("aslp_weight_bound", None, _vp, _i, _vp, _i, _vp, _vp, _i, _f, _f, _f, _f, 
 _sig("aslp_gemm_profile", None, _i)
 _sig("aslp_gemm_profile_reset", None)
 _sig("aslp_gru_seq_supported", _i, C.POINTER(GruSeq), _i)
+_sig("aslp_gru_seq_pieces", None, _i)
+_sig("aslp_gru_seq_pieces_get", _i)
+_sig("aslp_gru_seq_last_pieces", _i)
 _sig("aslp_gemm_force_tile", None, _i)
 _sig("aslp_gemm_last_tile", _i)
 _sig("aslp_gemm_split16_plan", _i, _i, _i, _i, _i, _i, _i, C.POINTER(GemmEpilogue), C.POINTER(GemmEpilogue), _i, _i, C.POINTER(_i))

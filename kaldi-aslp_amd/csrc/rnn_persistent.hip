@@ -1406,6 +1406,315 @@ __global__ void __launch_bounds__(512) gru_seq_bwd(aslp_gru_seq a, SeqStatus st,
   if (polls && g.lane == 0) __hip_atomic_fetch_add(st.abort_flag + 2, polls, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// ---- GruStreams, products on fp16 matrix instructions (opt-in: aslp_gru_seq_pieces, ASLP_GRU_SEQ_PIECES) -------------------------------
+// Same chains, placement check, hand-offs (gru_collect), fail[] vote, pieces (gru_piece / gru_publish), lane-pair gate arithmetic, buffers and
+// grid as gru_seq_fwd / gru_seq_bwd; only what lies between "operand collected in LDS" and "partial sums in red[]" differs, for all four
+// products.  v_mfma_f32_16x16x32_f16 takes the place of v_mfma_f32_4x4x1 with the operand split of lstm_seq_fwd_h:
+//  * weights, resident for the launch as B fragments: w sc = w_hi + w_lo, sc the power of two of the OUTPUT COLUMN that puts its largest |w|
+//    into [2^13, 2^14) (column maximum over the 8 waves through LDS, before the first timestep).  NP = 1 keeps w_hi alone.  Wave w holds the
+//    K slice [w kw, (w + 1) kw) of gru_kw as ceil(kw / 32) chunks; what lies past kw or K is a zero fragment.
+//  * left operand: A tile rows 0..7 = hi pieces of the chain's 8 streams, rows 8..15 = their lo' pieces (x s = hi + 2^-11 lo'); NP = 1: rows
+//    8..15 repeat rows 0..7.  s is a power of two per STREAM AND WAVE K SLICE, found by the wave over exactly the values it converts (two
+//    cross-lane maxima, no barrier): the partial sum is scaled back before it goes to red[], so no product carries a condition on magnitudes
+//    -- [d_z | d_r] and d_m may be 1e-20 or 1e5, h(0) whatever the caller stored.
+//  * Unlike lstm_seq_fwd_h the lanes build their A fragments straight from the fp32 rows gru_collect left in a_lds (lane (row, k group) reads
+//    its 8 values per chunk, converts, keeps hi or lo' by its row): no per-wave fp16 staging array, no second LDS round trip and no
+//    wave barrier, at the price of every value being converted by two lanes (one keeps hi, one lo').  The split products of the fp32 kernels
+//    (two K halves per wave) are whole 16 x 16 tiles here, so all four products leave 8 terms per output in the layout of the wide product
+//    ([wave][stream][kGruRPW], column 16 tile + cell) and gru_sum_wide adds them in wave order.
+// The two result halves are joined with v_permlane32_swap as in lstm_seq_fwd_h.
+// Measured (profiles/gru_seq_pieces.txt): at H = 512, S = 32 these kernels are SLOWER than the fp32-instruction ones (T = 60: 4.41 + 5.31 us
+// per timestep forward + backward with two pieces, 3.96 + 4.79 with one, against 3.63 + 4.04), hence off by default.
+// B fragments of one 16-column tile: row `row` of w (K-contiguous), this wave's K slice; cm: 8 x 64 floats of scratch (red[] before the first timestep).
+// Contains two workgroup barriers: every thread calls it.
+template <int NCH, int NP>
+__device__ __forceinline__ void gru_load_bh(half8 (&bh)[NCH], half8 (&bl)[NCH], float &inv_sc, const float *w, int ldw, int row, bool valid, int kb, int kw, int K,
+                                            float *cm, const GruGeom &g) {
+  const int hr = g.lane & 15, hg = g.lane >> 4;
+  const float *brow = w + (long)(valid ? row : 0) * ldw;
+  float wv[NCH][8];
+  float lmax = 0.f;
+#pragma unroll
+  for (int j = 0; j < NCH; j++) {
+    const int kl = 32 * j + 8 * hg, k0 = kb + kl;   // kw and K are multiples of 4: a piece of four is inside or outside as a whole
+#pragma unroll
+    for (int q = 0; q < 2; q++) {
+      const bool in = valid && kl + 4 * q < kw && k0 + 4 * q < K;
+      const f32x4 w4 = in ? *reinterpret_cast<const f32x4 *>(brow + k0 + 4 * q) : f32x4{0.f, 0.f, 0.f, 0.f};
+      wv[j][4 * q + 0] = w4.x; wv[j][4 * q + 1] = w4.y; wv[j][4 * q + 2] = w4.z; wv[j][4 * q + 3] = w4.w;
+      lmax = fmaxf(lmax, fmaxf(fmaxf(fabsf(w4.x), fabsf(w4.y)), fmaxf(fabsf(w4.z), fabsf(w4.w))));
+    }
+  }
+  cm[g.wave * 64 + g.lane] = lmax;
+  __syncthreads();
+  float cmax = 0.f;
+  for (int wq = 0; wq < 8; wq++)
+#pragma unroll
+    for (int g4 = 0; g4 < 4; g4++) cmax = fmaxf(cmax, cm[wq * 64 + 16 * g4 + hr]);
+  int e = 0;
+  (void)frexpf(cmax, &e);   // cmax = f 2^e, f in [0.5, 1)
+  const bool scaled = cmax > 0.f && cmax < 3.0e38f;
+  const float sc = scaled ? ldexpf(1.f, 14 - e) : 1.f;
+  inv_sc = scaled ? ldexpf(1.f, e - 14) : 1.f;
+#pragma unroll
+  for (int j = 0; j < NCH; j++)
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+      const float x = wv[j][i] * sc;
+      const _Float16 xh = (_Float16)x;
+      bh[j][i] = xh;
+      if constexpr (NP == 2) bl[j][i] = (_Float16)(x - (float)xh);
+    }
+  __syncthreads();   // the scratch is reused by the next tile and by the timesteps
+}
+// This wave's K slice [kb, kb + kw) of (8 streams x K) x (K x 16 NT columns), operands as described above; the wave's partial sums go to
+// red[wave][stream][16 tile + column] (pitch kGruRPW).  Nothing is read from a_lds past kw or K.
+template <int NCH, int NT, int NP>
+__device__ __forceinline__ void gru_product_h(float *red, const float *a_lds, int MP, const half8 (&bh)[NT][NCH], const half8 (&bl)[NT][NCH], const float (&inv_sc)[NT],
+                                              int kb, int kw, int K, const GruGeom &g) {
+  const int hr = g.lane & 15, hg = g.lane >> 4;
+  const float *arow = a_lds + (hr & 7) * MP;
+  float x[NCH][8];
+  unsigned amax = 0u;   // largest |x| of this lane's values, as bits (a NaN or infinity counts as the largest)
+#pragma unroll
+  for (int j = 0; j < NCH; j++) {
+    const int kl = 32 * j + 8 * hg, k0 = kb + kl;
+#pragma unroll
+    for (int q = 0; q < 2; q++) {
+      const bool in = kl + 4 * q < kw && k0 + 4 * q < K;
+      const f32x4 v = in ? *reinterpret_cast<const f32x4 *>(arow + k0 + 4 * q) : f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int i = 0; i < 4; i++) {
+        x[j][4 * q + i] = v[i];
+        amax = max(amax, __float_as_uint(v[i]) & 0x7fffffffu);
+      }
+    }
+  }
+  // the stream's maximum over the wave's slice: the four k groups of a row sit 16, 32 and 48 lanes apart
+  amax = max(amax, (unsigned)__shfl_xor((int)amax, 16));
+  amax = max(amax, (unsigned)__shfl_xor((int)amax, 32));
+  // s = 2^(140 - eb) puts the maximum 1.m 2^(eb - 127) into [2^13, 2^14).  eb below 27 (|x| < 2^-100, zero included) counts as 27, so that s
+  // stays finite; an infinity or NaN (eb = 255) keeps s = 1 and travels through the product as it would on the fp32 instruction.
+  const int eb0 = (int)(amax >> 23);
+  const int eb = eb0 == 255 ? 140 : max(eb0, 27);
+  const float s = __uint_as_float((unsigned)(267 - eb) << 23), inv_s = __uint_as_float((unsigned)(eb - 13) << 23);
+  half8 af[NCH];
+#pragma unroll
+  for (int j = 0; j < NCH; j++)
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+      const float xs = x[j][i] * s;
+      const _Float16 hi = (_Float16)xs;
+      if constexpr (NP == 2) af[j][i] = hr < 8 ? hi : (_Float16)((xs - (float)hi) * 2048.f);
+      else af[j][i] = hi;
+    }
+  f32x4 acc[NT];
+#pragma unroll
+  for (int tile = 0; tile < NT; tile++) acc[tile] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int j = 0; j < NCH; j++) {
+#pragma unroll
+    for (int tile = 0; tile < NT; tile++) acc[tile] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[j], bh[tile][j], acc[tile], 0, 0, 0);
+    if constexpr (NP == 2) {
+#pragma unroll
+      for (int tile = 0; tile < NT; tile++) acc[tile] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[j], bl[tile][j], acc[tile], 0, 0, 0);
+    }
+  }
+  // result register e of a lane = tile row 4 hg + e: stream 4 (hg & 1) + e, hi part in lanes 0..31, lo' part in lanes 32..63.  Its scale is
+  // the one of that stream's rows (every lane of row r and r + 8 holds stream r's).
+  const int hg2 = hg & 1, eodd = g.lane >> 5;
+  float inv_a[4];
+  {
+    float lo4[4], hi4[4];
+#pragma unroll
+    for (int e = 0; e < 4; e++) {
+      lo4[e] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(inv_s), e));
+      hi4[e] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(inv_s), 4 + e));
+    }
+#pragma unroll
+    for (int e = 0; e < 4; e++) inv_a[e] = hg2 ? hi4[e] : lo4[e];
+  }
+  float *rp = red + (g.wave * kChainStreams + 4 * hg2 + eodd) * kGruRPW + hr;
+#pragma unroll
+  for (int tile = 0; tile < NT; tile++) {
+    if constexpr (NP == 2) {
+      // x w = ([x_hi w] + 2^-11 [x_lo' w]) / (s sc); one v_permlane32_swap joins the halves of two result registers (see lstm_seq_fwd_h)
+      const float f = g.lane < 32 ? 1.0f : 0x1p-11f;
+#pragma unroll
+      for (int e = 0; e < 4; e += 2) {
+        const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(acc[tile][e] * f * inv_a[e]), __float_as_uint(acc[tile][e + 1] * f * inv_a[e + 1]), false, false);
+        rp[e * kGruRPW + 16 * tile] = (__uint_as_float(sw[0]) + __uint_as_float(sw[1])) * inv_sc[tile];
+      }
+    } else {
+      // one piece: both lane halves hold fp16(x s) w_hi of the same streams; the same store pattern, no join
+#pragma unroll
+      for (int e = 0; e < 4; e += 2) rp[e * kGruRPW + 16 * tile] = (eodd ? acc[tile][e + 1] * inv_a[e + 1] : acc[tile][e] * inv_a[e]) * inv_sc[tile];
+    }
+  }
+}
+
+// forward.  KW: K values per wave as in gru_seq_fwd (H <= 8 KW); NP: fp16 pieces per operand.
+template <int KW, int NP>
+__global__ void __launch_bounds__(512) gru_seq_fwd_h(aslp_gru_seq a, SeqStatus st, unsigned *place) {
+  static_assert(NP == 1 || NP == 2, "one or two fp16 pieces per operand");
+  constexpr int NCH = (KW + 31) / 32, MP = 8 * KW + 4;
+  __shared__ __attribute__((aligned(16))) float a_lds[kChainStreams * MP];
+  __shared__ float red[2][kGruRed];
+  __shared__ int fail[2][8];
+  __shared__ int place_flag;
+  const long t_entry = st.trace ? (long)wall_clock64() : 0;
+  const int SE = a.s_count > 0 ? a.s_begin + a.s_count : a.S;
+  const ChainRole R = chain_role(SE - a.s_begin, 1, a.H, st, place, &place_flag);
+  if (!R.active) return;
+  const int H = a.H, S = a.S, T = a.T, ld = a.ld;
+  const int omm = 2 * H, og = 3 * H, oh = 4 * H;
+  const int c0 = R.c0, s0 = a.s_begin + R.s0;
+  const GruGeom g = gru_geom();
+  const int kw = gru_kw(H), kb = g.wave * kw;
+  // B fragments, resident for the launch.  Round 1: tile = gate (z, r), column l & 15 = cell c0 + (l & 15); round 2: m of the same cells
+  half8 bh1[2][NCH], bl1[2][NCH], bh2[1][NCH], bl2[1][NCH];
+  float isc1[2], isc2[1];
+  {
+    const int cellb = c0 + (g.lane & 15);
+    gru_load_bh<NCH, NP>(bh1[0], bl1[0], isc1[0], a.w_zr, a.ldw_zr, cellb, cellb < H, kb, kw, H, red[0], g);
+    gru_load_bh<NCH, NP>(bh1[1], bl1[1], isc1[1], a.w_zr, a.ldw_zr, H + cellb, cellb < H, kb, kw, H, red[0], g);
+    gru_load_bh<NCH, NP>(bh2[0], bl2[0], isc2[0], a.w_m, a.ldw_m, cellb, cellb < H, kb, kw, H, red[0], g);
+  }
+  const int s = s0 + g.sl, cell = c0 + g.cc;
+  const bool live = threadIdx.x < 256 && s < SE && cell < H;
+  const int cq = live ? cell : 0, sq = live ? s : 0;
+  float hp = live ? a.y[(long)sq * ld + oh + cq] : 0.f;   // h(0): the carried history in row block 0
+  unsigned polls = 0u;
+  for (int step = 0; step < T; step++) {
+    const int t = 1 + step;
+    float *ys = a.y + ((long)t * S + sq) * ld;
+    const float xg = live ? ys[g.role * H + cq] : 0.f;
+    const float xm = (live && g.role == 0) ? ys[omm + cq] : 0.f;
+    // ---- round 1: h(t-1) -> z, r, g ------------------------------------------------------------------------------
+    bool ok = gru_collect<2>(a.y + (long)(t - 1) * S * ld, ld, SE, s0, oh, H, a_lds, MP, st, polls);
+    if (g.lane == 0) fail[0][g.wave] = ok ? 0 : 1;
+    __syncthreads();
+    gru_product_h<NCH, 2, NP>(red[0], a_lds, MP, bh1, bl1, isc1, kb, kw, H, g);
+    __syncthreads();
+    if (seq_failed(fail, 0)) return;
+    float gate = 0.f;
+    if (threadIdx.x < 256) gate = sigmoid_ref(xg + gru_sum_wide(red[0], g.sl, g.role * 16 + g.cc));
+    const float zz = gate;                       // meaningful on lane 0 of the pair
+    const float gg = gate * hp;                  // g = r .* h(t-1), meaningful on lane 1
+    {
+      const u32x4 pk = gru_piece(gg);
+      if (live && g.role == 1 && (g.cc & 3) == 0) gru_publish(pk, a.y + (long)t * S * ld, s * ld + og + cell, R.local);
+      if (live) ys[g.role * H + cell] = gate;
+    }
+    // ---- round 2: g(t) -> m, h -----------------------------------------------------------------------------------
+    ok = gru_collect<2>(a.y + (long)t * S * ld, ld, SE, s0, og, H, a_lds, MP, st, polls);
+    if (g.lane == 0) fail[1][g.wave] = ok ? 0 : 1;
+    __syncthreads();
+    gru_product_h<NCH, 1, NP>(red[1], a_lds, MP, bh2, bl2, isc2, kb, kw, H, g);
+    __syncthreads();
+    if (seq_failed(fail, 1)) return;
+    float mm = 0.f, hh = 0.f;
+    if (threadIdx.x < 256 && g.role == 0) {
+      mm = tanh_ref(xm + gru_sum_wide(red[1], g.sl, g.cc));
+      hh = hp - hp * zz + zz * mm;
+    }
+    {
+      const u32x4 pk = gru_piece(hh);
+      if (live && g.role == 0 && (g.cc & 3) == 0) gru_publish(pk, a.y + (long)t * S * ld, s * ld + oh + cell, R.local);
+      if (live && g.role == 0) ys[omm + cell] = mm;
+    }
+    // h(t) to both lanes of the pair
+    const float from_left = __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(hh), 0x111, 0xF, 0xF, true));  // row_shr:1
+    hp = g.role == 0 ? hh : from_left;
+  }
+  if (st.trace && threadIdx.x == 0) {
+    unsigned long long *tr = st.trace + (st.epoch & 7u) * 2048u;
+    tr[2 * blockIdx.x] = (unsigned long long)t_entry; tr[2 * blockIdx.x + 1] = wall_clock64();
+  }
+  if (polls && g.lane == 0) __hip_atomic_fetch_add(st.abort_flag + 2, polls, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// backward.  KW1 / KW2: K values per wave of the two products as in gru_seq_bwd (2H <= 8 KW1, H <= 8 KW2); NP: fp16 pieces per operand.
+template <int KW1, int KW2, int NP>
+__global__ void __launch_bounds__(512) gru_seq_bwd_h(aslp_gru_seq a, SeqStatus st, unsigned *place) {
+  static_assert(NP == 1 || NP == 2, "one or two fp16 pieces per operand");
+  constexpr int NC1 = (KW1 + 31) / 32, NC2 = (KW2 + 31) / 32, MP = 8 * KW1 + 4;
+  __shared__ __attribute__((aligned(16))) float a_lds[kChainStreams * MP];
+  __shared__ float red[2][kGruRed];
+  __shared__ int fail[2][8];
+  __shared__ int place_flag;
+  const long t_entry = st.trace ? (long)wall_clock64() : 0;
+  const int SE = a.s_count > 0 ? a.s_begin + a.s_count : a.S;
+  const ChainRole R = chain_role(SE - a.s_begin, 1, a.H, st, place, &place_flag);
+  if (!R.active) return;
+  const int H = a.H, S = a.S, T = a.T, ld = a.ld;
+  const int orr = H, omm = 2 * H, og = 3 * H, oh = 4 * H;
+  const int c0 = R.c0, s0 = a.s_begin + R.s0;
+  const GruGeom g = gru_geom();
+  const int kw1 = gru_kw(2 * H), k1 = g.wave * kw1, kw2 = gru_kw(H), k2 = g.wave * kw2;
+  half8 bha[1][NC1], bla[1][NC1], bhb[1][NC2], blb[1][NC2];
+  float isca[1], iscb[1];
+  {
+    const int cellb = c0 + (g.lane & 15);
+    gru_load_bh<NC1, NP>(bha[0], bla[0], isca[0], a.w_zr, a.ldw_zr, cellb, cellb < H, k1, kw1, 2 * H, red[0], g);
+    gru_load_bh<NC2, NP>(bhb[0], blb[0], iscb[0], a.w_m, a.ldw_m, cellb, cellb < H, k2, kw2, H, red[0], g);
+  }
+  const int s = s0 + g.sl, cell = c0 + g.cc;
+  const bool live = threadIdx.x < 256 && s < SE && cell < H;
+  const int cq = live ? cell : 0, sq = live ? s : 0;
+  float dhn = 0.f, zn = 0.f, dgn = 0.f, rn = 0.f;   // d_h, z, d_g, r of this pair at t + 1 (row block T + 1 is zero)
+  unsigned polls = 0u;
+  for (int step = 0; step < T; step++) {
+    const int t = T - step;
+    const long o = ((long)t * S + sq) * ld;
+    const float yz = live ? a.y[o + cq] : 0.f, yr = live ? a.y[o + orr + cq] : 0.f, ym = live ? a.y[o + omm + cq] : 0.f;
+    const float hprev = live ? a.y[o - (long)S * ld + oh + cq] : 0.f;   // h(t-1)
+    const float dh_ext = live ? a.d[o + oh + cq] : 0.f;                  // the loss's share, stored before the launch
+    // ---- round 1: [d_z | d_r](t+1) W_zr_h -> d_h, d_m ----------------------------------------------------------------
+    bool ok = true;
+    if (step > 0) ok = gru_collect<4>(a.d + (long)(t + 1) * S * ld, ld, SE, s0, 0, 2 * H, a_lds, MP, st, polls);
+    if (g.lane == 0) fail[0][g.wave] = ok ? 0 : 1;
+    __syncthreads();
+    if (step > 0) gru_product_h<NC1, 1, NP>(red[0], a_lds, MP, bha, bla, isca, k1, kw1, 2 * H, g);
+    __syncthreads();
+    if (seq_failed(fail, 0)) return;
+    float dh = 0.f, dm = 0.f;
+    if (threadIdx.x < 256) {   // both lanes of the pair form d_h (lane 1 needs it for nothing; the arithmetic is uniform)
+      const float prod = step > 0 ? gru_sum_wide(red[0], g.sl, g.cc) : 0.f;
+      dh = dh_ext + prod + dhn - dhn * zn + dgn * rn;
+      dm = dtanh(ym, dh * yz);
+    }
+    {
+      const u32x4 pk = gru_piece(dm);
+      if (live && g.role == 0 && (g.cc & 3) == 0) gru_publish(pk, a.d + (long)t * S * ld, s * ld + omm + cell, R.local);
+      if (live && g.role == 0) a.d[o + oh + cell] = dh;
+    }
+    // ---- round 2: d_m(t) W_m_g -> d_g, d_r, d_z ----------------------------------------------------------------------
+    ok = gru_collect<2>(a.d + (long)t * S * ld, ld, SE, s0, omm, H, a_lds, MP, st, polls);
+    if (g.lane == 0) fail[1][g.wave] = ok ? 0 : 1;
+    __syncthreads();
+    gru_product_h<NC2, 1, NP>(red[1], a_lds, MP, bhb, blb, iscb, k2, kw2, H, g);
+    __syncthreads();
+    if (seq_failed(fail, 1)) return;
+    float dg = 0.f, dzr = 0.f;
+    if (threadIdx.x < 256) {
+      dg = gru_sum_wide(red[1], g.sl, g.cc);
+      dzr = g.role == 0 ? dsigm(yz, dh * ym - dh * hprev) : dsigm(yr, dg * hprev);
+    }
+    {
+      const u32x4 pk = gru_piece(dzr);   // lane 0 of the pairs: four d_z; lane 1: four d_r
+      if (live && (g.cc & 3) == 0) gru_publish(pk, a.d + (long)t * S * ld, s * ld + g.role * H + cell, R.local);
+      if (live && g.role == 0) a.d[o + og + cell] = dg;
+    }
+    dhn = dh; zn = yz; dgn = dg; rn = yr;
+  }
+  if (st.trace && threadIdx.x == 0) {
+    unsigned long long *tr = st.trace + (st.epoch & 7u) * 2048u;
+    tr[2 * blockIdx.x] = (unsigned long long)t_entry; tr[2 * blockIdx.x + 1] = wall_clock64();
+  }
+  if (polls && g.lane == 0) __hip_atomic_fetch_add(st.abort_flag + 2, polls, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
 // Finishes the bias / peephole gradients of one direction from the per-chain sums lstm_seq_bwd left (grad_partial): thread = (quantity k,
 // cell c); chains of the direction added in order; then momentum, clip and the folded SGD step as rnn_vec_grads_kernel does them.
 struct SeqVecGradArgs {
@@ -1637,7 +1946,26 @@ SeqKernelB pick_bwd(bool cifg, int C) {
 }
 
 typedef void (*GruKernel)(aslp_gru_seq, SeqStatus, unsigned *);
-GruKernel pick_gru(bool backward, int H) {
+// fp16 pieces per operand of the GRU recurrences' products: 0 = the fp32 instruction (gru_seq_fwd / gru_seq_bwd, the default), 1 / 2 =
+// gru_seq_fwd_h / gru_seq_bwd_h (ASLP_GRU_SEQ_PIECES, aslp_gru_seq_pieces()).  Independent of every LSTM and GEMM switch, and none of those
+// reaches the GRU kernels.
+int g_gru_pieces_override = -1;   // aslp_gru_seq_pieces(): -1 = the environment decides
+int gru_pieces() {
+  static const int env = [] {
+    const char *e = getenv("ASLP_GRU_SEQ_PIECES");
+    return (e != nullptr && (e[0] == '1' || e[0] == '2') && e[1] == 0) ? e[0] - '0' : 0;
+  }();
+  return g_gru_pieces_override >= 0 ? g_gru_pieces_override : env;
+}
+template <int NP>
+GruKernel pick_gru_h(bool backward, int H) {
+  if (H <= 128) return backward ? gru_seq_bwd_h<32, 16, NP> : gru_seq_fwd_h<16, NP>;
+  if (H <= 512) return backward ? gru_seq_bwd_h<128, 64, NP> : gru_seq_fwd_h<64, NP>;
+  return nullptr;
+}
+GruKernel pick_gru(bool backward, int H, int np) {
+  if (np == 1) return pick_gru_h<1>(backward, H);
+  if (np == 2) return pick_gru_h<2>(backward, H);
   if (H <= 128) return backward ? gru_seq_bwd<32, 16> : gru_seq_fwd<16>;
   if (H <= 512) return backward ? gru_seq_bwd<128, 64> : gru_seq_fwd<64>;
   return nullptr;
@@ -1763,7 +2091,7 @@ static void launch_seq(const aslp_lstm_seq *a, bool backward, const char *who) {
   t_last_pieces = split ? np : 0;
 }
 
-int aslp_gru_seq_supported(const aslp_gru_seq *a, int backward) {
+static int gru_seq_supported_np(const aslp_gru_seq *a, int backward, int np) {
   static const bool disabled = (getenv("ASLP_LSTM_PERSISTENT") != nullptr && getenv("ASLP_LSTM_PERSISTENT")[0] == '0') ||
                                (getenv("ASLP_GRU_PERSISTENT") != nullptr && getenv("ASLP_GRU_PERSISTENT")[0] == '0');
   if (disabled || !a || a->T <= 0 || a->S <= 0 || a->H <= 0 || (a->H & 3) || (a->ld & 3)) return 0;
@@ -1771,11 +2099,17 @@ int aslp_gru_seq_supported(const aslp_gru_seq *a, int backward) {
   const int ns = a->s_count > 0 ? a->s_count : a->S;
   const int nsg = (ns + kChainStreams - 1) / kChainStreams, wpc = (a->H + kCellsPerWg - 1) / kCellsPerWg;
   if (nsg > kMaxChains || wpc > kMaxWgPerChain) return 0;   // <= 64 streams per launch, H <= 512
-  return grid_fits(reinterpret_cast<const void *>(pick_gru(backward != 0, a->H)), 512, (long)kMaxChains * wpc) ? 1 : 0;
+  return grid_fits(reinterpret_cast<const void *>(pick_gru(backward != 0, a->H, np)), 512, (long)kMaxChains * wpc) ? 1 : 0;
 }
+// (the kernel probed is the one launch_gru would start now)
+int aslp_gru_seq_supported(const aslp_gru_seq *a, int backward) { return gru_seq_supported_np(a, backward, gru_pieces()); }
+void aslp_gru_seq_pieces(int n) { g_gru_pieces_override = (n >= 0 && n <= 2) ? n : -1; }
+int aslp_gru_seq_pieces_get(void) { return gru_pieces(); }
 
+thread_local int t_last_gru_pieces = 0;   // aslp_gru_seq_last_pieces()
 static void launch_gru(const aslp_gru_seq *a, bool backward, const char *who) {
-  if (!gru_args_ok(a, backward) || !aslp_gru_seq_supported(a, backward ? 1 : 0)) {
+  const int np = gru_pieces();   // read once: the probe below and the launch see the same kernel
+  if (!gru_args_ok(a, backward) || !gru_seq_supported_np(a, backward ? 1 : 0, np)) {
     set_error(std::string(who) + ": arguments outside what the persistent kernel supports (check aslp_gru_seq_supported first)");
     return;
   }
@@ -1785,8 +2119,10 @@ static void launch_gru(const aslp_gru_seq *a, bool backward, const char *who) {
   SeqStatus st = {rt.abort_flag, rt.host_err_dev, nullptr, ((rt.timing_mode == 3 && !backward) || (rt.timing_mode == 4 && backward)) ? rt.timing + 8 : nullptr,
                   rt.epoch, 0u};
   const int wpc = (a->H + kCellsPerWg - 1) / kCellsPerWg;
-  hipLaunchKernelGGL(pick_gru(backward, a->H), dim3(kMaxChains * wpc), dim3(512), 0, cur_stream(), *a, st, rt.place);
+  hipLaunchKernelGGL(pick_gru(backward, a->H, np), dim3(kMaxChains * wpc), dim3(512), 0, cur_stream(), *a, st, rt.place);
+  t_last_gru_pieces = np;
 }
+int aslp_gru_seq_last_pieces(void) { return t_last_gru_pieces; }
 void aslp_gru_seq_forward(const aslp_gru_seq *a) { launch_gru(a, false, "aslp_gru_seq_forward"); }
 void aslp_gru_seq_backward(const aslp_gru_seq *a) { launch_gru(a, true, "aslp_gru_seq_backward"); }
 

@@ -85,6 +85,26 @@ def lstm_operand_pieces(n):
         lib.aslp_lstm_operand_pieces(before)
 
 
+def set_gru_seq_pieces(n):
+    """fp16 pieces per operand of the products inside the persistent GRU recurrences (aslp_gru_seq_pieces): 0 = the fp32 instruction (default),
+    2 = hi and lo' on the fp16 instruction (fp32-equivalent operands), 1 = hi alone (fp16 operands, fp32 accumulation), -1 = what
+    ASLP_GRU_SEQ_PIECES said"""
+    lib.aslp_gru_seq_pieces(int(n))
+
+
+@contextlib.contextmanager
+def gru_seq_pieces(n):
+    """persistent GRU recurrences inside the block multiply with n pieces per operand (0 = the fp32 instruction); the setting in force before
+    comes back on exit (pinned as an explicit setting, as lstm_operand_pieces does; set_gru_seq_pieces(-1) hands the choice back to the
+    environment)"""
+    before = lib.aslp_gru_seq_pieces_get()
+    lib.aslp_gru_seq_pieces(int(n))
+    try:
+        yield
+    finally:
+        lib.aslp_gru_seq_pieces(before)
+
+
 def set_lstm_step_split16(on):
     """split-fp16 products on the per-timestep LSTM path (aslp_lstm_step_split16): 1 = the step kernels multiply on the fp16 instruction with
     lstm_operand_pieces pieces per operand, 0 = the fp32 instruction (default), -1 = what ASLP_LSTM_STEP_SPLIT_F16 said"""
