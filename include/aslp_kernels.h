@@ -596,7 +596,7 @@ int aslp_gru_seq_supported(const aslp_gru_seq *a, int backward);
 void aslp_gru_seq_forward(const aslp_gru_seq *a);
 void aslp_gru_seq_backward(const aslp_gru_seq *a);
 /* fp16 pieces per operand of the four recurrent products inside aslp_gru_seq_forward / _backward.  0 (default): the fp32 instruction
- * v_mfma_f32_4x4x1 (gru_seq_fwd / gru_seq_bwd).  1 / 2 (opt-in): v_mfma_f32_16x16x32_f16 (gru_seq_fwd_h / gru_seq_bwd_h) with that many pieces --
+ * v_mfma_f32_4x4x1.  1 / 2 (opt-in): v_mfma_f32_16x16x32_f16 with that many pieces (NP of gru_seq_fwd / gru_seq_bwd, csrc/rnn_persistent.hip) --
  * 2: every operand as hi and lo', fp32-equivalent; 1: the hi piece alone, i.e. fp16(x s) / s times fp16(W sc) / sc accumulated in fp32 in a fixed
  * order, s a power of two per stream and K slice of a wave, sc one per output column, so no magnitude of h(0), [d_z | d_r] or d_m is excluded.
  * The weights still arrive as fp32 matrices; everything outside the products stays fp32.  Any other n hands the choice to ASLP_GRU_SEQ_PIECES

@@ -1115,15 +1115,33 @@ __global__ void __launch_bounds__(512) lstm_seq_bwd_h(aslp_lstm_seq a, SeqStatus
 //   backward  d_h(t) += [d_z | d_r](t+1) W_zr_h -> d_h, d_m                    then   d_g(t) = d_m(t) W_m_g -> d_r, d_z
 // so every timestep is two rounds of "collect the chain's left operand (8 streams x K, published by the chain's workgroups in the
 // previous round) into LDS -- multiply with this workgroup's columns of the recurrent matrix (registers, resident for the launch,
-// v_mfma_f32_4x4x1, 8 waves split K) -- finish the 8 x 16 (stream, cell) pairs -- publish 16-byte pieces".  Chains, placement check,
-// "the data is its own flag" hand-off and the bounded spins are those of the LSTM kernels above; GruStreams is unidirectional, so
+// 8 waves split K) -- partial sums meet in red[] -- finish the 8 x 16 (stream, cell) pairs -- publish 16-byte pieces".  Chains, placement
+// check, "the data is its own flag" hand-off and the bounded spins are those of the LSTM kernels above; GruStreams is unidirectional, so
 // S = 32 gives 4 chains of 32 workgroups (H = 512).  A lane pair owns a (stream, cell): lane 0 of the pair z (forward) / d_z, d_h,
 // d_m, d_g (backward), lane 1 r and g / d_r; h(t-1) and the terms the backward step carries from t+1 never leave the pair's registers.
+// One kernel template per pass; NP chooses the engine of its two products.  Only what lies between "operand collected in LDS" and "partial sums
+// in red[]" depends on it (B fragments, a lane's K offset, the product calls) and the sum that reads red[]; all else is one text for both engines.
 //
-// One MFMA instruction is 16 independent 4 x 4 blocks.  The first forward product has 32 columns per workgroup (z and r of its 16
-// cells): blocks = 2 stream quads x 8 column quads ("wide").  The other three products have 16 columns: blocks = 2 stream quads x 4
-// column quads x 2 HALVES OF THE WAVE'S K SLICE ("split") -- no idle blocks, half the instructions and half the weight registers;
-// the two halves' partial sums are two of the 16 terms the epilogue adds per output.
+// NP = 0, v_mfma_f32_4x4x1 (the default).  One instruction is 16 independent 4 x 4 blocks.  The first forward product has 32 columns per
+// workgroup (z and r of its 16 cells): blocks = 2 stream quads x 8 column quads ("wide").  The other three products have 16 columns:
+// blocks = 2 stream quads x 4 column quads x 2 HALVES OF THE WAVE'S K SLICE ("split") -- no idle blocks, half the instructions and half
+// the weight registers; the two halves' partial sums are two of the 16 terms the epilogue adds per output (gru_sum_split).
+//
+// NP = 1 / 2, v_mfma_f32_16x16x32_f16 on one / two fp16 pieces per operand (opt-in: aslp_gru_seq_pieces, ASLP_GRU_SEQ_PIECES), split as in lstm_seq_fwd_h:
+//  * weights, resident for the launch as B fragments: w sc = w_hi + w_lo, sc the power of two of the OUTPUT COLUMN that puts its largest |w|
+//    into [2^13, 2^14) (column maximum over the 8 waves through LDS, before the first timestep).  NP = 1 keeps w_hi alone.  Wave w holds the
+//    K slice [w kw, (w + 1) kw) of gru_kw as ceil(kw / 32) chunks; what lies past kw or K is a zero fragment.
+//  * left operand: A tile rows 0..7 = hi pieces of the chain's 8 streams, rows 8..15 = their lo' pieces (x s = hi + 2^-11 lo'); NP = 1: rows
+//    8..15 repeat rows 0..7.  s is a power of two per STREAM AND WAVE K SLICE, found by the wave over exactly the values it converts (two
+//    cross-lane maxima, no barrier): the partial sum is scaled back before it goes to red[], so no product carries a condition on magnitudes
+//    -- [d_z | d_r] and d_m may be 1e-20 or 1e5, h(0) whatever the caller stored.
+//  * Unlike lstm_seq_fwd_h the lanes build their A fragments straight from the fp32 rows gru_collect left in a_lds (lane (row, k group) reads
+//    its 8 values per chunk, converts, keeps hi or lo' by its row): no per-wave fp16 staging array, no second LDS round trip and no wave
+//    barrier, at the price of every value being converted by two lanes.  The split products are whole 16 x 16 tiles here, so all four
+//    products leave 8 terms per output in the layout of the wide product ([wave][stream][kGruRPW], column 16 tile + cell) and gru_sum_wide
+//    adds them in wave order.  The two result halves are joined with v_permlane32_swap as in lstm_seq_fwd_h.
+// Measured (profiles/gru_seq_pieces.txt): at H = 512, S = 32 the fp16 engine is SLOWER than the fp32 one (T = 60: 4.41 + 5.31 us
+// per timestep forward + backward with two pieces, 3.96 + 4.79 with one, against 3.63 + 4.04), hence off by default.
 struct GruGeom {
   int lane, wave, qs, qc, jl, kh, col16, pair, role, sl, cc;
 };
@@ -1248,183 +1266,6 @@ __device__ __forceinline__ void gru_publish(const u32x4 &pk, float *rowblock, in
 }
 // K values per wave for a reduction of length K: a multiple of 8 (so that the split products' halves are whole fragments), 8 waves cover K
 __device__ __forceinline__ int gru_kw(int K) { return ((K + 63) / 64) * 8; }
-
-// grid 8 * ceil(H / 16) workgroups of 512 threads (chains >= S / 8 leave at once).  KW: K values per wave, H <= 8 * KW.
-template <int KW>
-__global__ void __launch_bounds__(512) gru_seq_fwd(aslp_gru_seq a, SeqStatus st, unsigned *place) {
-  constexpr int NBW = KW / 4, NBS = KW / 8, MP = 8 * KW + 4;
-  __shared__ __attribute__((aligned(16))) float a_lds[kChainStreams * MP];
-  __shared__ float red[2][kGruRed];
-  __shared__ int fail[2][8];
-  __shared__ int place_flag;
-  const long t_entry = st.trace ? (long)wall_clock64() : 0;
-  const int SE = a.s_count > 0 ? a.s_begin + a.s_count : a.S;
-  const ChainRole R = chain_role(SE - a.s_begin, 1, a.H, st, place, &place_flag);
-  if (!R.active) return;
-  const int H = a.H, S = a.S, T = a.T, ld = a.ld;
-  const int omm = 2 * H, og = 3 * H, oh = 4 * H;
-  const int c0 = R.c0, s0 = a.s_begin + R.s0;
-  const GruGeom g = gru_geom();
-  const int kw = gru_kw(H), kb = g.wave * kw, kbs = kb + g.kh * (kw / 2);
-  // B fragments, resident for the launch.  Round 1 (wide): column n = 4 qc + jl is gate n >> 4 (z, r) of cell c0 + (n & 15);
-  // round 2 (split): column col16 is m of cell c0 + col16, this lane's half of the wave's K slice
-  f32x4 bw1[NBW], bw2[NBS];
-  {
-    const int n = 4 * g.qc + g.jl;
-    gru_load_b<NBW>(bw1, a.w_zr, a.ldw_zr, (n >> 4) * H + c0 + (n & 15), c0 + (n & 15) < H, kb, kw, H);
-    gru_load_b<NBS>(bw2, a.w_m, a.ldw_m, c0 + g.col16, c0 + g.col16 < H, kbs, kw / 2, H);
-  }
-  const int s = s0 + g.sl, cell = c0 + g.cc;
-  const bool live = threadIdx.x < 256 && s < SE && cell < H;
-  const int cq = live ? cell : 0, sq = live ? s : 0;
-  float hp = live ? a.y[(long)sq * ld + oh + cq] : 0.f;   // h(0): the carried history in row block 0
-  unsigned polls = 0u;
-  for (int step = 0; step < T; step++) {
-    const int t = 1 + step;
-    float *ys = a.y + ((long)t * S + sq) * ld;
-    // the x-parts (+ bias) of this pair: written before the launch, requested before the hand-off wait
-    const float xg = live ? ys[g.role * H + cq] : 0.f;
-    const float xm = (live && g.role == 0) ? ys[omm + cq] : 0.f;
-    // ---- round 1: h(t-1) -> z, r, g ------------------------------------------------------------------------------
-    bool ok = gru_collect<2>(a.y + (long)(t - 1) * S * ld, ld, SE, s0, oh, H, a_lds, MP, st, polls);
-    if (g.lane == 0) fail[0][g.wave] = ok ? 0 : 1;
-    __syncthreads();
-    gru_store_wide(red[0], gru_product<NBW>(a_lds, MP, bw1, kb, kw, H, g), g);
-    __syncthreads();
-    if (seq_failed(fail, 0)) return;
-    float gate = 0.f;
-    if (threadIdx.x < 256) gate = sigmoid_ref(xg + gru_sum_wide(red[0], g.sl, g.role * 16 + g.cc));
-    const float zz = gate;                       // meaningful on lane 0 of the pair
-    const float gg = gate * hp;                  // g = r .* h(t-1), meaningful on lane 1
-    {
-      const u32x4 pk = gru_piece(gg);
-      if (live && g.role == 1 && (g.cc & 3) == 0) gru_publish(pk, a.y + (long)t * S * ld, s * ld + og + cell, R.local);
-      if (live) ys[g.role * H + cell] = gate;
-    }
-    // ---- round 2: g(t) -> m, h -----------------------------------------------------------------------------------
-    ok = gru_collect<2>(a.y + (long)t * S * ld, ld, SE, s0, og, H, a_lds, MP, st, polls);
-    if (g.lane == 0) fail[1][g.wave] = ok ? 0 : 1;
-    __syncthreads();
-    gru_store_split(red[1], gru_product<NBS>(a_lds, MP, bw2, kbs, kw / 2, H, g), g);
-    __syncthreads();
-    if (seq_failed(fail, 1)) return;
-    float mm = 0.f, hh = 0.f;
-    if (threadIdx.x < 256 && g.role == 0) {
-      mm = tanh_ref(xm + gru_sum_split(red[1], g.sl, g.cc));
-      hh = hp - hp * zz + zz * mm;
-    }
-    {
-      const u32x4 pk = gru_piece(hh);
-      if (live && g.role == 0 && (g.cc & 3) == 0) gru_publish(pk, a.y + (long)t * S * ld, s * ld + oh + cell, R.local);
-      if (live && g.role == 0) ys[omm + cell] = mm;
-    }
-    // h(t) to both lanes of the pair
-    const float from_left = __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(hh), 0x111, 0xF, 0xF, true));  // row_shr:1
-    hp = g.role == 0 ? hh : from_left;
-  }
-  if (st.trace && threadIdx.x == 0) {
-    unsigned long long *tr = st.trace + (st.epoch & 7u) * 2048u;
-    tr[2 * blockIdx.x] = (unsigned long long)t_entry; tr[2 * blockIdx.x + 1] = wall_clock64();
-  }
-  if (polls && g.lane == 0) __hip_atomic_fetch_add(st.abort_flag + 2, polls, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// backward: a.w_zr = W_zr_h^T [H x 2H], a.w_m = W_m_g^T [H x H] (K-contiguous rows of this workgroup's 16 cells); both products split.
-// KW1 / KW2: K values per wave of the two products (2H <= 8 KW1, H <= 8 KW2).
-template <int KW1, int KW2>
-__global__ void __launch_bounds__(512) gru_seq_bwd(aslp_gru_seq a, SeqStatus st, unsigned *place) {
-  constexpr int NB1 = KW1 / 8, NB2 = KW2 / 8, MP = 8 * KW1 + 4;
-  __shared__ __attribute__((aligned(16))) float a_lds[kChainStreams * MP];
-  __shared__ float red[2][kGruRed];
-  __shared__ int fail[2][8];
-  __shared__ int place_flag;
-  const long t_entry = st.trace ? (long)wall_clock64() : 0;
-  const int SE = a.s_count > 0 ? a.s_begin + a.s_count : a.S;
-  const ChainRole R = chain_role(SE - a.s_begin, 1, a.H, st, place, &place_flag);
-  if (!R.active) return;
-  const int H = a.H, S = a.S, T = a.T, ld = a.ld;
-  const int orr = H, omm = 2 * H, og = 3 * H, oh = 4 * H;
-  const int c0 = R.c0, s0 = a.s_begin + R.s0;
-  const GruGeom g = gru_geom();
-  const int kw1 = gru_kw(2 * H), k1 = g.wave * kw1 + g.kh * (kw1 / 2), kw2 = gru_kw(H), k2 = g.wave * kw2 + g.kh * (kw2 / 2);
-  f32x4 bwa[NB1], bwb[NB2];
-  gru_load_b<NB1>(bwa, a.w_zr, a.ldw_zr, c0 + g.col16, c0 + g.col16 < H, k1, kw1 / 2, 2 * H);
-  gru_load_b<NB2>(bwb, a.w_m, a.ldw_m, c0 + g.col16, c0 + g.col16 < H, k2, kw2 / 2, H);
-  const int s = s0 + g.sl, cell = c0 + g.cc;
-  const bool live = threadIdx.x < 256 && s < SE && cell < H;
-  const int cq = live ? cell : 0, sq = live ? s : 0;
-  float dhn = 0.f, zn = 0.f, dgn = 0.f, rn = 0.f;   // d_h, z, d_g, r of this pair at t + 1 (row block T + 1 is zero)
-  unsigned polls = 0u;
-  for (int step = 0; step < T; step++) {
-    const int t = T - step;
-    const long o = ((long)t * S + sq) * ld;
-    const float yz = live ? a.y[o + cq] : 0.f, yr = live ? a.y[o + orr + cq] : 0.f, ym = live ? a.y[o + omm + cq] : 0.f;
-    const float hprev = live ? a.y[o - (long)S * ld + oh + cq] : 0.f;   // h(t-1)
-    const float dh_ext = live ? a.d[o + oh + cq] : 0.f;                  // the loss's share, stored before the launch
-    // ---- round 1: [d_z | d_r](t+1) W_zr_h -> d_h, d_m ----------------------------------------------------------------
-    bool ok = true;
-    if (step > 0) ok = gru_collect<4>(a.d + (long)(t + 1) * S * ld, ld, SE, s0, 0, 2 * H, a_lds, MP, st, polls);
-    if (g.lane == 0) fail[0][g.wave] = ok ? 0 : 1;
-    __syncthreads();
-    if (step > 0) gru_store_split(red[0], gru_product<NB1>(a_lds, MP, bwa, k1, kw1 / 2, 2 * H, g), g);
-    __syncthreads();
-    if (seq_failed(fail, 0)) return;
-    float dh = 0.f, dm = 0.f;
-    if (threadIdx.x < 256) {   // both lanes of the pair form d_h (lane 1 needs it for nothing; the arithmetic is uniform)
-      const float prod = step > 0 ? gru_sum_split(red[0], g.sl, g.cc) : 0.f;
-      dh = dh_ext + prod + dhn - dhn * zn + dgn * rn;
-      dm = dtanh(ym, dh * yz);
-    }
-    {
-      const u32x4 pk = gru_piece(dm);
-      if (live && g.role == 0 && (g.cc & 3) == 0) gru_publish(pk, a.d + (long)t * S * ld, s * ld + omm + cell, R.local);
-      if (live && g.role == 0) a.d[o + oh + cell] = dh;
-    }
-    // ---- round 2: d_m(t) W_m_g -> d_g, d_r, d_z ----------------------------------------------------------------------
-    ok = gru_collect<2>(a.d + (long)t * S * ld, ld, SE, s0, omm, H, a_lds, MP, st, polls);
-    if (g.lane == 0) fail[1][g.wave] = ok ? 0 : 1;
-    __syncthreads();
-    gru_store_split(red[1], gru_product<NB2>(a_lds, MP, bwb, k2, kw2 / 2, H, g), g);
-    __syncthreads();
-    if (seq_failed(fail, 1)) return;
-    float dg = 0.f, dzr = 0.f;
-    if (threadIdx.x < 256) {
-      dg = gru_sum_split(red[1], g.sl, g.cc);
-      dzr = g.role == 0 ? dsigm(yz, dh * ym - dh * hprev) : dsigm(yr, dg * hprev);
-    }
-    {
-      const u32x4 pk = gru_piece(dzr);   // lane 0 of the pairs: four d_z; lane 1: four d_r
-      if (live && (g.cc & 3) == 0) gru_publish(pk, a.d + (long)t * S * ld, s * ld + g.role * H + cell, R.local);
-      if (live && g.role == 0) a.d[o + og + cell] = dg;
-    }
-    dhn = dh; zn = yz; dgn = dg; rn = yr;
-  }
-  if (st.trace && threadIdx.x == 0) {
-    unsigned long long *tr = st.trace + (st.epoch & 7u) * 2048u;
-    tr[2 * blockIdx.x] = (unsigned long long)t_entry; tr[2 * blockIdx.x + 1] = wall_clock64();
-  }
-  if (polls && g.lane == 0) __hip_atomic_fetch_add(st.abort_flag + 2, polls, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// ---- GruStreams, products on fp16 matrix instructions (opt-in: aslp_gru_seq_pieces, ASLP_GRU_SEQ_PIECES) -------------------------------
-// Same chains, placement check, hand-offs (gru_collect), fail[] vote, pieces (gru_piece / gru_publish), lane-pair gate arithmetic, buffers and
-// grid as gru_seq_fwd / gru_seq_bwd; only what lies between "operand collected in LDS" and "partial sums in red[]" differs, for all four
-// products.  v_mfma_f32_16x16x32_f16 takes the place of v_mfma_f32_4x4x1 with the operand split of lstm_seq_fwd_h:
-//  * weights, resident for the launch as B fragments: w sc = w_hi + w_lo, sc the power of two of the OUTPUT COLUMN that puts its largest |w|
-//    into [2^13, 2^14) (column maximum over the 8 waves through LDS, before the first timestep).  NP = 1 keeps w_hi alone.  Wave w holds the
-//    K slice [w kw, (w + 1) kw) of gru_kw as ceil(kw / 32) chunks; what lies past kw or K is a zero fragment.
-//  * left operand: A tile rows 0..7 = hi pieces of the chain's 8 streams, rows 8..15 = their lo' pieces (x s = hi + 2^-11 lo'); NP = 1: rows
-//    8..15 repeat rows 0..7.  s is a power of two per STREAM AND WAVE K SLICE, found by the wave over exactly the values it converts (two
-//    cross-lane maxima, no barrier): the partial sum is scaled back before it goes to red[], so no product carries a condition on magnitudes
-//    -- [d_z | d_r] and d_m may be 1e-20 or 1e5, h(0) whatever the caller stored.
-//  * Unlike lstm_seq_fwd_h the lanes build their A fragments straight from the fp32 rows gru_collect left in a_lds (lane (row, k group) reads
-//    its 8 values per chunk, converts, keeps hi or lo' by its row): no per-wave fp16 staging array, no second LDS round trip and no
-//    wave barrier, at the price of every value being converted by two lanes (one keeps hi, one lo').  The split products of the fp32 kernels
-//    (two K halves per wave) are whole 16 x 16 tiles here, so all four products leave 8 terms per output in the layout of the wide product
-//    ([wave][stream][kGruRPW], column 16 tile + cell) and gru_sum_wide adds them in wave order.
-// The two result halves are joined with v_permlane32_swap as in lstm_seq_fwd_h.
-// Measured (profiles/gru_seq_pieces.txt): at H = 512, S = 32 these kernels are SLOWER than the fp32-instruction ones (T = 60: 4.41 + 5.31 us
-// per timestep forward + backward with two pieces, 3.96 + 4.79 with one, against 3.63 + 4.04), hence off by default.
 // B fragments of one 16-column tile: row `row` of w (K-contiguous), this wave's K slice; cm: 8 x 64 floats of scratch (red[] before the first timestep).
 // Contains two workgroup barriers: every thread calls it.
 template <int NCH, int NP>
@@ -1553,16 +1394,19 @@ __device__ __forceinline__ void gru_product_h(float *red, const float *a_lds, in
   }
 }
 
-// forward.  KW: K values per wave as in gru_seq_fwd (H <= 8 KW); NP: fp16 pieces per operand.
+// forward: grid 8 * ceil(H / 16) workgroups of 512 threads (chains >= S / 8 leave at once).  KW: K values per wave, H <= 8 * KW; NP: the engine.
+// (Parts of the two kernels tried as shared functions of scalars and pointers, each alone, judged by the 12 kernels' text: the trace / polls tail moved
+// all 12 and the counts of 5; stays a copy.  The others are noted where they stand.)
 template <int KW, int NP>
-__global__ void __launch_bounds__(512) gru_seq_fwd_h(aslp_gru_seq a, SeqStatus st, unsigned *place) {
-  static_assert(NP == 1 || NP == 2, "one or two fp16 pieces per operand");
-  constexpr int NCH = (KW + 31) / 32, MP = 8 * KW + 4;
+__global__ void __launch_bounds__(512) gru_seq_fwd(aslp_gru_seq a, SeqStatus st, unsigned *place) {
+  static_assert(NP >= 0 && NP <= 2, "0: the fp32 instruction; 1 or 2: fp16 pieces per operand");
+  constexpr int NBW = KW / 4, NBS = KW / 8, NCH = (KW + 31) / 32, MP = 8 * KW + 4;
   __shared__ __attribute__((aligned(16))) float a_lds[kChainStreams * MP];
   __shared__ float red[2][kGruRed];
   __shared__ int fail[2][8];
   __shared__ int place_flag;
   const long t_entry = st.trace ? (long)wall_clock64() : 0;
+  // (these two lines as a shared function: the text of all 12 kernels moved, no count; stay a copy in both kernels)
   const int SE = a.s_count > 0 ? a.s_begin + a.s_count : a.S;
   const ChainRole R = chain_role(SE - a.s_begin, 1, a.H, st, place, &place_flag);
   if (!R.active) return;
@@ -1570,11 +1414,17 @@ __global__ void __launch_bounds__(512) gru_seq_fwd_h(aslp_gru_seq a, SeqStatus s
   const int omm = 2 * H, og = 3 * H, oh = 4 * H;
   const int c0 = R.c0, s0 = a.s_begin + R.s0;
   const GruGeom g = gru_geom();
-  const int kw = gru_kw(H), kb = g.wave * kw;
-  // B fragments, resident for the launch.  Round 1: tile = gate (z, r), column l & 15 = cell c0 + (l & 15); round 2: m of the same cells
+  const int kw = gru_kw(H), kb = g.wave * kw, kbs = kb + g.kh * (kw / 2);
+  // B fragments, resident for the launch; the set of the other engine leaves no code.  fp32, round 1 (wide): column n = 4 qc + jl is gate n >> 4 (z, r) of cell
+  // c0 + (n & 15); round 2 (split): column col16 is m of cell c0 + col16, this lane's K half.  fp16: tile = gate (z, r; then m), column l & 15 = cell c0 + (l & 15)
+  f32x4 bw1[NBW], bw2[NBS];
   half8 bh1[2][NCH], bl1[2][NCH], bh2[1][NCH], bl2[1][NCH];
   float isc1[2], isc2[1];
-  {
+  if constexpr (NP == 0) {
+    const int n = 4 * g.qc + g.jl;
+    gru_load_b<NBW>(bw1, a.w_zr, a.ldw_zr, (n >> 4) * H + c0 + (n & 15), c0 + (n & 15) < H, kb, kw, H);
+    gru_load_b<NBS>(bw2, a.w_m, a.ldw_m, c0 + g.col16, c0 + g.col16 < H, kbs, kw / 2, H);
+  } else {
     const int cellb = c0 + (g.lane & 15);
     gru_load_bh<NCH, NP>(bh1[0], bl1[0], isc1[0], a.w_zr, a.ldw_zr, cellb, cellb < H, kb, kw, H, red[0], g);
     gru_load_bh<NCH, NP>(bh1[1], bl1[1], isc1[1], a.w_zr, a.ldw_zr, H + cellb, cellb < H, kb, kw, H, red[0], g);
@@ -1582,19 +1432,22 @@ __global__ void __launch_bounds__(512) gru_seq_fwd_h(aslp_gru_seq a, SeqStatus s
   }
   const int s = s0 + g.sl, cell = c0 + g.cc;
   const bool live = threadIdx.x < 256 && s < SE && cell < H;
-  const int cq = live ? cell : 0, sq = live ? s : 0;
+  const int cq = live ? cell : 0, sq = live ? s : 0;   // (s .. sq as a shared function: same text, but ten parameters for three lines; stay a copy)
   float hp = live ? a.y[(long)sq * ld + oh + cq] : 0.f;   // h(0): the carried history in row block 0
   unsigned polls = 0u;
   for (int step = 0; step < T; step++) {
     const int t = 1 + step;
     float *ys = a.y + ((long)t * S + sq) * ld;
+    // the x-parts (+ bias) of this pair: written before the launch, requested before the hand-off wait
     const float xg = live ? ys[g.role * H + cq] : 0.f;
     const float xm = (live && g.role == 0) ? ys[omm + cq] : 0.f;
+    // (a round's frame -- collect, post, barrier, product as a lambda, barrier, vote -- as a shared function: all 12 moved, gru_seq_fwd<64, 0> 206 -> 202 VGPRs; stays a copy, four times)
     // ---- round 1: h(t-1) -> z, r, g ------------------------------------------------------------------------------
     bool ok = gru_collect<2>(a.y + (long)(t - 1) * S * ld, ld, SE, s0, oh, H, a_lds, MP, st, polls);
     if (g.lane == 0) fail[0][g.wave] = ok ? 0 : 1;
     __syncthreads();
-    gru_product_h<NCH, 2, NP>(red[0], a_lds, MP, bh1, bl1, isc1, kb, kw, H, g);
+    if constexpr (NP == 0) gru_store_wide(red[0], gru_product<NBW>(a_lds, MP, bw1, kb, kw, H, g), g);
+    else gru_product_h<NCH, 2, NP>(red[0], a_lds, MP, bh1, bl1, isc1, kb, kw, H, g);
     __syncthreads();
     if (seq_failed(fail, 0)) return;
     float gate = 0.f;
@@ -1610,12 +1463,13 @@ __global__ void __launch_bounds__(512) gru_seq_fwd_h(aslp_gru_seq a, SeqStatus s
     ok = gru_collect<2>(a.y + (long)t * S * ld, ld, SE, s0, og, H, a_lds, MP, st, polls);
     if (g.lane == 0) fail[1][g.wave] = ok ? 0 : 1;
     __syncthreads();
-    gru_product_h<NCH, 1, NP>(red[1], a_lds, MP, bh2, bl2, isc2, kb, kw, H, g);
+    if constexpr (NP == 0) gru_store_split(red[1], gru_product<NBS>(a_lds, MP, bw2, kbs, kw / 2, H, g), g);
+    else gru_product_h<NCH, 1, NP>(red[1], a_lds, MP, bh2, bl2, isc2, kb, kw, H, g);
     __syncthreads();
     if (seq_failed(fail, 1)) return;
     float mm = 0.f, hh = 0.f;
     if (threadIdx.x < 256 && g.role == 0) {
-      mm = tanh_ref(xm + gru_sum_wide(red[1], g.sl, g.cc));
+      mm = tanh_ref(xm + (NP == 0 ? gru_sum_split(red[1], g.sl, g.cc) : gru_sum_wide(red[1], g.sl, g.cc)));
       hh = hp - hp * zz + zz * mm;
     }
     {
@@ -1634,11 +1488,12 @@ __global__ void __launch_bounds__(512) gru_seq_fwd_h(aslp_gru_seq a, SeqStatus s
   if (polls && g.lane == 0) __hip_atomic_fetch_add(st.abort_flag + 2, polls, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// backward.  KW1 / KW2: K values per wave of the two products as in gru_seq_bwd (2H <= 8 KW1, H <= 8 KW2); NP: fp16 pieces per operand.
+// backward: a.w_zr = W_zr_h^T [H x 2H], a.w_m = W_m_g^T [H x H] (K-contiguous rows of this workgroup's 16 cells); both products split
+// under the fp32 engine.  KW1 / KW2: K values per wave of the two products (2H <= 8 KW1, H <= 8 KW2); NP: the engine.
 template <int KW1, int KW2, int NP>
-__global__ void __launch_bounds__(512) gru_seq_bwd_h(aslp_gru_seq a, SeqStatus st, unsigned *place) {
-  static_assert(NP == 1 || NP == 2, "one or two fp16 pieces per operand");
-  constexpr int NC1 = (KW1 + 31) / 32, NC2 = (KW2 + 31) / 32, MP = 8 * KW1 + 4;
+__global__ void __launch_bounds__(512) gru_seq_bwd(aslp_gru_seq a, SeqStatus st, unsigned *place) {
+  static_assert(NP >= 0 && NP <= 2, "0: the fp32 instruction; 1 or 2: fp16 pieces per operand");
+  constexpr int NB1 = KW1 / 8, NB2 = KW2 / 8, NC1 = (KW1 + 31) / 32, NC2 = (KW2 + 31) / 32, MP = 8 * KW1 + 4;
   __shared__ __attribute__((aligned(16))) float a_lds[kChainStreams * MP];
   __shared__ float red[2][kGruRed];
   __shared__ int fail[2][8];
@@ -1651,10 +1506,15 @@ __global__ void __launch_bounds__(512) gru_seq_bwd_h(aslp_gru_seq a, SeqStatus s
   const int orr = H, omm = 2 * H, og = 3 * H, oh = 4 * H;
   const int c0 = R.c0, s0 = a.s_begin + R.s0;
   const GruGeom g = gru_geom();
-  const int kw1 = gru_kw(2 * H), k1 = g.wave * kw1, kw2 = gru_kw(H), k2 = g.wave * kw2;
+  const int kw1 = gru_kw(2 * H), kw2 = gru_kw(H);   // (fp32: a lane's K offset is its half of the wave's slice)
+  const int k1 = g.wave * kw1 + (NP == 0 ? g.kh * (kw1 / 2) : 0), k2 = g.wave * kw2 + (NP == 0 ? g.kh * (kw2 / 2) : 0);
+  f32x4 bwa[NB1], bwb[NB2];
   half8 bha[1][NC1], bla[1][NC1], bhb[1][NC2], blb[1][NC2];
   float isca[1], iscb[1];
-  {
+  if constexpr (NP == 0) {
+    gru_load_b<NB1>(bwa, a.w_zr, a.ldw_zr, c0 + g.col16, c0 + g.col16 < H, k1, kw1 / 2, 2 * H);
+    gru_load_b<NB2>(bwb, a.w_m, a.ldw_m, c0 + g.col16, c0 + g.col16 < H, k2, kw2 / 2, H);
+  } else {
     const int cellb = c0 + (g.lane & 15);
     gru_load_bh<NC1, NP>(bha[0], bla[0], isca[0], a.w_zr, a.ldw_zr, cellb, cellb < H, k1, kw1, 2 * H, red[0], g);
     gru_load_bh<NC2, NP>(bhb[0], blb[0], iscb[0], a.w_m, a.ldw_m, cellb, cellb < H, k2, kw2, H, red[0], g);
@@ -1675,12 +1535,15 @@ __global__ void __launch_bounds__(512) gru_seq_bwd_h(aslp_gru_seq a, SeqStatus s
     if (step > 0) ok = gru_collect<4>(a.d + (long)(t + 1) * S * ld, ld, SE, s0, 0, 2 * H, a_lds, MP, st, polls);
     if (g.lane == 0) fail[0][g.wave] = ok ? 0 : 1;
     __syncthreads();
-    if (step > 0) gru_product_h<NC1, 1, NP>(red[0], a_lds, MP, bha, bla, isca, k1, kw1, 2 * H, g);
+    if (step > 0) {
+      if constexpr (NP == 0) gru_store_split(red[0], gru_product<NB1>(a_lds, MP, bwa, k1, kw1 / 2, 2 * H, g), g);
+      else gru_product_h<NC1, 1, NP>(red[0], a_lds, MP, bha, bla, isca, k1, kw1, 2 * H, g);
+    }
     __syncthreads();
     if (seq_failed(fail, 0)) return;
     float dh = 0.f, dm = 0.f;
     if (threadIdx.x < 256) {   // both lanes of the pair form d_h (lane 1 needs it for nothing; the arithmetic is uniform)
-      const float prod = step > 0 ? gru_sum_wide(red[0], g.sl, g.cc) : 0.f;
+      const float prod = step > 0 ? (NP == 0 ? gru_sum_split(red[0], g.sl, g.cc) : gru_sum_wide(red[0], g.sl, g.cc)) : 0.f;
       dh = dh_ext + prod + dhn - dhn * zn + dgn * rn;
       dm = dtanh(ym, dh * yz);
     }
@@ -1693,12 +1556,13 @@ __global__ void __launch_bounds__(512) gru_seq_bwd_h(aslp_gru_seq a, SeqStatus s
     ok = gru_collect<2>(a.d + (long)t * S * ld, ld, SE, s0, omm, H, a_lds, MP, st, polls);
     if (g.lane == 0) fail[1][g.wave] = ok ? 0 : 1;
     __syncthreads();
-    gru_product_h<NC2, 1, NP>(red[1], a_lds, MP, bhb, blb, iscb, k2, kw2, H, g);
+    if constexpr (NP == 0) gru_store_split(red[1], gru_product<NB2>(a_lds, MP, bwb, k2, kw2 / 2, H, g), g);
+    else gru_product_h<NC2, 1, NP>(red[1], a_lds, MP, bhb, blb, iscb, k2, kw2, H, g);
     __syncthreads();
     if (seq_failed(fail, 1)) return;
     float dg = 0.f, dzr = 0.f;
     if (threadIdx.x < 256) {
-      dg = gru_sum_wide(red[1], g.sl, g.cc);
+      dg = NP == 0 ? gru_sum_split(red[1], g.sl, g.cc) : gru_sum_wide(red[1], g.sl, g.cc);
       dzr = g.role == 0 ? dsigm(yz, dh * ym - dh * hprev) : dsigm(yr, dg * hprev);
     }
     {
@@ -1946,9 +1810,8 @@ SeqKernelB pick_bwd(bool cifg, int C) {
 }
 
 typedef void (*GruKernel)(aslp_gru_seq, SeqStatus, unsigned *);
-// fp16 pieces per operand of the GRU recurrences' products: 0 = the fp32 instruction (gru_seq_fwd / gru_seq_bwd, the default), 1 / 2 =
-// gru_seq_fwd_h / gru_seq_bwd_h (ASLP_GRU_SEQ_PIECES, aslp_gru_seq_pieces()).  Independent of every LSTM and GEMM switch, and none of those
-// reaches the GRU kernels.
+// NP of gru_seq_fwd / gru_seq_bwd: 0 = the fp32 instruction (the default), 1 / 2 = fp16 pieces per operand (ASLP_GRU_SEQ_PIECES,
+// aslp_gru_seq_pieces()).  Independent of every LSTM and GEMM switch, and none of those reaches the GRU kernels.
 int g_gru_pieces_override = -1;   // aslp_gru_seq_pieces(): -1 = the environment decides
 int gru_pieces() {
   static const int env = [] {
@@ -1958,22 +1821,19 @@ int gru_pieces() {
   return g_gru_pieces_override >= 0 ? g_gru_pieces_override : env;
 }
 template <int NP>
-GruKernel pick_gru_h(bool backward, int H) {
-  if (H <= 128) return backward ? gru_seq_bwd_h<32, 16, NP> : gru_seq_fwd_h<16, NP>;
-  if (H <= 512) return backward ? gru_seq_bwd_h<128, 64, NP> : gru_seq_fwd_h<64, NP>;
+GruKernel pick_gru_np(bool backward, int H) {
+  if (H <= 128) return backward ? gru_seq_bwd<32, 16, NP> : gru_seq_fwd<16, NP>;
+  if (H <= 512) return backward ? gru_seq_bwd<128, 64, NP> : gru_seq_fwd<64, NP>;
   return nullptr;
 }
 GruKernel pick_gru(bool backward, int H, int np) {
-  if (np == 1) return pick_gru_h<1>(backward, H);
-  if (np == 2) return pick_gru_h<2>(backward, H);
-  if (H <= 128) return backward ? gru_seq_bwd<32, 16> : gru_seq_fwd<16>;
-  if (H <= 512) return backward ? gru_seq_bwd<128, 64> : gru_seq_fwd<64>;
-  return nullptr;
+  return np == 1 ? pick_gru_np<1>(backward, H) : np == 2 ? pick_gru_np<2>(backward, H) : pick_gru_np<0>(backward, H);
 }
+// the scalars of a launch, for the probe (which may come before the buffers exist) and for the launch
+bool gru_dims_ok(const aslp_gru_seq *a) { return a && a->T > 0 && a->S > 0 && a->H > 0 && (a->H & 3) == 0 && (a->ld & 3) == 0; }
 bool gru_args_ok(const aslp_gru_seq *a, bool backward) {
-  return a && a->y && a->w_zr && a->w_m && (!backward || a->d) && a->T > 0 && a->S > 0 && a->H > 0 && (a->H & 3) == 0 && (a->ld & 3) == 0 &&
-         (a->ldw_zr & 3) == 0 && (a->ldw_m & 3) == 0 && a->ld >= 5 * a->H && aligned16(a->y) && aligned16(a->w_zr) && aligned16(a->w_m) &&
-         (!backward || aligned16(a->d));
+  return gru_dims_ok(a) && a->y && a->w_zr && a->w_m && (!backward || a->d) && (a->ldw_zr & 3) == 0 && (a->ldw_m & 3) == 0 && a->ld >= 5 * a->H &&
+         aligned16(a->y) && aligned16(a->w_zr) && aligned16(a->w_m) && (!backward || aligned16(a->d));
 }
 
 bool seq_args_ok(const aslp_lstm_seq *a) {
@@ -2094,7 +1954,7 @@ static void launch_seq(const aslp_lstm_seq *a, bool backward, const char *who) {
 static int gru_seq_supported_np(const aslp_gru_seq *a, int backward, int np) {
   static const bool disabled = (getenv("ASLP_LSTM_PERSISTENT") != nullptr && getenv("ASLP_LSTM_PERSISTENT")[0] == '0') ||
                                (getenv("ASLP_GRU_PERSISTENT") != nullptr && getenv("ASLP_GRU_PERSISTENT")[0] == '0');
-  if (disabled || !a || a->T <= 0 || a->S <= 0 || a->H <= 0 || (a->H & 3) || (a->ld & 3)) return 0;
+  if (disabled || !gru_dims_ok(a)) return 0;
   if (a->s_begin < 0 || a->s_count < 0 || a->s_begin + a->s_count > a->S) return 0;
   const int ns = a->s_count > 0 ? a->s_count : a->S;
   const int nsg = (ns + kChainStreams - 1) / kChainStreams, wpc = (a->H + kCellsPerWg - 1) / kCellsPerWg;

@@ -1,4 +1,4 @@
-"""The 12 persistent GRU kernels of csrc/rnn_persistent.hip (gru_seq_fwd, gru_seq_bwd on the fp32 instruction; gru_seq_fwd_h, gru_seq_bwd_h with
+"""The 12 persistent GRU kernels of csrc/rnn_persistent.hip (gru_seq_fwd<KW, NP>, gru_seq_bwd<KW1, KW2, NP>: NP = 0 the fp32 instruction, 1 / 2
 one / two fp16 pieces per operand; two rungs of H each) against the float64 model of the aslp_gru_seq contract (tests/gru_seq_ref.py, pinned
 to the oracle by tests/test_gru_seq_ref_cpu.py, which also counts that the cases below launch all 12).
 

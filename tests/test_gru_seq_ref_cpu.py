@@ -86,14 +86,14 @@ def test_round11_is_fp16s_significand():
 # ---- the case list covers every instantiation --------------------------------------------------------------------------------------------
 
 def launched(c, pieces):
-    """(family, rung, pieces template parameter) of the forward and the backward launch of a case: pick_gru restated"""
+    """(family, rung, pieces template parameter NP) of the forward and the backward launch of a case: pick_gru restated"""
     rung = 0 if c.H <= 128 else 1
-    assert c.H <= 512
-    return [("gru_seq_fwd_h" if pieces else "gru_seq_fwd", rung, pieces or None), ("gru_seq_bwd_h" if pieces else "gru_seq_bwd", rung, pieces or None)]
+    assert c.H <= 512 and pieces in (0, 1, 2)
+    return [("gru_seq_fwd", rung, pieces), ("gru_seq_bwd", rung, pieces)]
 
 
 def test_cases_reach_all_12_kernels():
-    every = {(f + ("_h" if p else ""), rung, p) for f in ("gru_seq_fwd", "gru_seq_bwd") for rung in (0, 1) for p in (None, 1, 2)}
+    every = {(f, rung, p) for f in ("gru_seq_fwd", "gru_seq_bwd") for rung in (0, 1) for p in (0, 1, 2)}
     assert len(every) == 12 and ref.PIECES == (0, 2, 1)
     hit = {}
     for c in ref.CASES:
@@ -102,7 +102,7 @@ def test_cases_reach_all_12_kernels():
                 hit.setdefault(inst, []).append(c)
     assert set(hit) == every, sorted(every - set(hit), key=str)
     for inst, cases in sorted(hit.items(), key=str):
-        print("  %-14s rung %d pieces %-4s <- H = %s" % (inst + (sorted({c.H for c in cases}),)))
+        print("  %-11s rung %d pieces %d <- H = %s" % (inst + (sorted({c.H for c in cases}),)))
 
 
 def test_case_list_holds_what_the_issue_names():
