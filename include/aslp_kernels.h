@@ -251,8 +251,8 @@ void aslp_gemm_split16_tile(int cfg);
  * are then those of A16.  The producers write both planes in either mode, so the mode may change between any two products.  One-plane
  * products run the 32 x 64 / 64 x 128 / 128 x 128 tiles of gemm_s16_glds and report 404 / 408 / 411 through aslp_gemm_last_tile(); shapes
  * the split path does not serve, and everything under aslp_gemm_split16(0), stay on the fp32 instruction.  The products inside the recurrent
- * layers' persistent and per-timestep kernels keep their two pieces.  -1 hands the choice back to ASLP_GEMM_PLANES (1 | 2, default 2,
- * read once per process).  Process-wide, like aslp_gemm_split16. */
+ * layers' persistent and per-timestep kernels keep their two pieces.  -1 hands the choice back to ASLP_GEMM_PLANES (1 | 2, default 2 -- 1
+ * under aslp_fp16_operands --, read once per process).  Process-wide, like aslp_gemm_split16. */
 void aslp_gemm_operand_planes(int n);
 int aslp_gemm_operand_planes_get(void);
 /* Prepared operands of such products: the two fp16 planes of an fp32 matrix, in the matrix' own layout (csrc/split16.h), made once and
@@ -458,11 +458,11 @@ void aslp_lstm_step_forward(const aslp_lstm_step *a);
 void aslp_lstm_step_backward(const aslp_lstm_step *a);
 /* Split-fp16 products on the per-timestep path (opt-in).  on = 1: aslp_lstm_step_forward_h / _backward_h below take their products
  * m(t-1) W_eff^T and dGATES(next) W_eff on v_mfma_f32_32x32x16_f16 with operands as fp16 pieces; 0: off; -1 hands the choice to
- * ASLP_LSTM_STEP_SPLIT_F16 (read once, "1" = on; default off).  Process-wide.  With the switch off nothing changes anywhere: the _h entry
+ * ASLP_LSTM_STEP_SPLIT_F16 (read once, "1" = on, "0" = off; unset: off, or on under aslp_fp16_operands).  Process-wide.  With the switch off nothing changes anywhere: the _h entry
  * points run the fp32-instruction kernels of aslp_lstm_step_forward / _backward, bit for bit.  With it on the piece count is
  * aslp_lstm_operand_pieces_get(): 2 = hi and lo' (fp32-equivalent operands), 1 = the hi piece alone.  ASLP_LSTM_SPLIT_F16 (the
- * persistent kernels' switch) does not concern this path.  Not covered: the GRU step kernels, the unfused path, the step-0 W_first
- * product.
+ * persistent kernels' switch) does not concern this path.  Not covered: the GRU step kernels (their own switch: aslp_gru_step_pieces), the unfused path, the
+ * step-0 W_first product.
  * Numeric contract.  Weights: the caller hands in the planes of W_eff (forward) / W_eff^T (backward) in the format of csrc/split16.h
  * (W s = hi + 2^-11 lo', s = 2^up from the bound in *w_slot; layout of the matrix, ldp halves per row, zeros in the padding), made once
  * per training step (aslp_planes_convert, or the engine's PlaneSet::ConvertMany).  The kernels read 16 halves of k per step up to K
@@ -540,7 +540,7 @@ void aslp_lstm_split16(int on);
 /* fp16 pieces per operand inside those kernels.  2 (default): hi and lo', fp32-equivalent operands.  1 (opt-in): the hi piece alone -- the
  * recurrent product is fp16(m(t-1)) (fp16(W sc) / sc)^T forward and fp16(dG s) / s times the hi piece of the W_eff rows backward, accumulated in
  * fp32 in a fixed order; everything outside the product stays fp32.  Any other n hands the choice back to ASLP_LSTM_PIECES (read once; "1"
- * selects one piece).  aslp_lstm_split16(0) / ASLP_LSTM_SPLIT_F16=0 wins: the fp32 instruction has no pieces.  Independent of
+ * selects one piece, "2" two; unset: 2, or 1 under aslp_fp16_operands).  aslp_lstm_split16(0) / ASLP_LSTM_SPLIT_F16=0 wins: the fp32 instruction has no pieces.  Independent of
  * aslp_gemm_operand_planes.  The step-0 W_first product and the GRU kernels are not affected; the per-timestep path (csrc/rnn_fused.hip)
  * follows the piece count only under its own switch aslp_lstm_step_split16(1) (above), which aslp_lstm_split16(0) does not turn off. */
 void aslp_lstm_operand_pieces(int n);
@@ -601,8 +601,8 @@ void aslp_gru_seq_backward(const aslp_gru_seq *a);
  * order, s a power of two per stream and K slice of a wave, sc one per output column, so no magnitude of h(0), [d_z | d_r] or d_m is excluded.
  * The weights still arrive as fp32 matrices; everything outside the products stays fp32.  Any other n hands the choice to ASLP_GRU_SEQ_PIECES
  * (read once; "0", "1", "2"; unset or anything else counts as 0).  Independent of aslp_lstm_operand_pieces, aslp_lstm_split16,
- * aslp_lstm_step_split16 and aslp_gemm_operand_planes, none of which reaches the GRU kernels; aslp_gru_step_* (csrc/gru_fused.hip) and the unfused
- * path are not affected.  aslp_gru_seq_supported probes the kernel the setting selects. */
+ * aslp_lstm_step_split16 and aslp_gemm_operand_planes, none of which reaches the GRU kernels; aslp_gru_step_* (csrc/gru_fused.hip, with a switch of its own:
+ * aslp_gru_step_pieces) and the unfused path are not affected.  aslp_fp16_operands leaves this switch at 0 (the fp16 form measured slower).  aslp_gru_seq_supported probes the kernel the setting selects. */
 void aslp_gru_seq_pieces(int n);
 int aslp_gru_seq_pieces_get(void);
 /* What the calling thread's latest aslp_gru_seq_forward / _backward launched: 0 = the fp32 instruction, 1 / 2 = the fp16 kernels with that many
@@ -616,6 +616,54 @@ int aslp_gru_step_supported(int H);
 void aslp_gru_step_forward(float *y_cur, const float *y_prev, const float *w_zr_h, int ld_zr, const float *w_m_g, int ld_mg, int ld, int S, int H);
 void aslp_gru_step_backward(float *d_cur, const float *d_next, const float *y_cur, const float *y_next, const float *y_prev, const float *w_zr_h_t,
                             int ld_zr_t, const float *w_m_g_t, int ld_mg_t, int ld, int S, int H, int has_next);
+/* fp16-piece products in those four kernels (opt-in).  aslp_gru_step_pieces(n): 0 = off (default), 1 / 2 = aslp_gru_step_forward_h /
+ * _backward_h below take their products h(t-1) W_zr_h^T, g(t) W_m_g^T, [d_z | d_r](t+1) W_zr_h and d_m(t) W_m_g on v_mfma_f32_32x32x16_f16
+ * with that many fp16 pieces per operand (gru_step_fwd1_h / fwd2_h / bwd1_h / bwd2_h<NP>); any other n hands the choice to
+ * ASLP_GRU_STEP_PIECES (read once; "0", "1", "2").  Process-wide.  At 0 nothing changes anywhere: the _h entry points run the
+ * fp32-instruction kernels of aslp_gru_step_forward / _backward, bit for bit, and do not look at the planes.  Under aslp_fp16_operands
+ * (below) the default becomes 1: measured on an MI355X at H = 1024 the one-piece recurrence takes 42.7 us per timestep against 52.2 on
+ * the fp32 instruction (S = 64) and 37.3 against 46.7 (S = 20), DESIGN section 7.  Independent of aslp_gru_seq_pieces and of every LSTM and
+ * GEMM switch.
+ * Numeric contract.  Weights: the caller hands in the planes of W_zr_h [2H x H] and W_m_g [H x H] (forward) / of their K-contiguous
+ * transposes [H x 2H] and [H x H] (backward) in the format of csrc/split16.h (W s = hi + 2^-11 lo', s = 2^up the power of two that puts
+ * the matrix's largest |w| -- the bound in *slot -- into [2^13, 2^14); layout of the matrix, ldp halves per row, zeros in the padding), made
+ * once per pass (aslp_planes_convert, or the engine's PlaneSet::ConvertMany).  The kernels read 16 halves of k per step up to K rounded up
+ * to 16: they rely on ldp >= that (the planes' rows are padded to 64) and on the padding being zero; the entry points refuse a shorter ldp
+ * and unaligned planes through the error slot.  fp32 operand columns >= K are never addressed and enter as zeros.  Forward: h(t-1) and
+ * g(t) are split as they are loaded, without a scale (both are bounded by 1): hi = fp16(x), lo' = fp16((x - hi) 2^11).  Backward:
+ * [d_z | d_r](t+1) (K = 2H) and d_m(t) (K = H) are split as they are loaded behind a power-of-two scale per stream row and run of up to 128
+ * consecutive k, runs counted from the start of each wave's K slice; the scale puts the run's largest finite |value| into [2^13, 2^14), an
+ * all-zero run takes scale 1 and adds an exact zero, and each run is unscaled into the wave's fp32 sum before the next.
+ * Two pieces: hi hi + 2^-11 (hi lo' + lo' hi) per k step, lo' lo' dropped; one piece: hi hi.  fp32 accumulation k step by k step per
+ * wave (a contiguous K slice each), the waves' tiles added through LDS in wave order: bit-reproducible from run to run and from process to
+ * process.  Everything outside the four products is the fp32 code of the entry points above.  H a multiple of 4, not necessarily of 16. */
+typedef struct aslp_gru_step_h_ {
+  const void *zr_hi, *zr_lo;      /* fp16 planes of W_zr_h (forward) / W_zr_h^T (backward), 16-byte aligned (lo is not read with one piece) */
+  const unsigned *zr_slot;        /* device word, bits of the bound those planes are scaled by */
+  const void *mg_hi, *mg_lo;      /* the same for W_m_g / W_m_g^T */
+  const unsigned *mg_slot;
+  int ldp_zr, ldp_mg;             /* halves per plane row: a multiple of 8, >= K rounded up to 16 (K = H; 2H for W_zr_h^T) */
+} aslp_gru_step_h;
+void aslp_gru_step_pieces(int n);
+int aslp_gru_step_pieces_get(void);   /* 0 / 1 / 2: what is in force */
+/* the arguments of aslp_gru_step_forward / _backward, then the planes (may be NULL while the switch is at 0) */
+void aslp_gru_step_forward_h(float *y_cur, const float *y_prev, const float *w_zr_h, int ld_zr, const float *w_m_g, int ld_mg, int ld, int S, int H,
+                             const aslp_gru_step_h *planes);
+void aslp_gru_step_backward_h(float *d_cur, const float *d_next, const float *y_cur, const float *y_next, const float *y_prev, const float *w_zr_h_t,
+                              int ld_zr_t, const float *w_m_g_t, int ld_mg_t, int ld, int S, int H, int has_next, const aslp_gru_step_h *planes);
+/* What the calling thread's latest aslp_gru_step_forward(_h) / _backward(_h) multiplied with: 0 = the fp32 instruction, 1 / 2 = fp16 pieces. */
+int aslp_gru_step_last_pieces(void);
+/* One switch for fp16 operands (ASLP_FP16_OPERANDS=1).  on = 1 / 0; -1 = what ASLP_FP16_OPERANDS said (read once; only "1" turns it on).
+ * Process-wide.  It launches nothing and changes nothing by itself: it changes the DEFAULT of the per-site switches.  A site asks, in this
+ * order, (1) its own setter, if that holds an explicit value, (2) its own environment variable, if set to a value it accepts, (3) this
+ * switch, if on, (4) its old default -- so every existing variable and setter keeps its meaning and wins.  With it on the defaults are
+ *   aslp_gemm_operand_planes 1,  aslp_lstm_operand_pieces 1,  aslp_lstm_step_split16 on,  aslp_gru_step_pieces 1,  aslp_gru_seq_pieces 0:
+ * the fast mixed-precision mode, not a numerics-uniform one -- a site joins only where its one-piece form is faster than the site's default,
+ * and the persistent GRU kernels measured slower with one piece than on the fp32 instruction, so they stay on it.  aslp_gemm_split16(0) / ASLP_GEMM_SPLIT_F16=0 and aslp_lstm_split16(0)
+ * / ASLP_LSTM_SPLIT_F16=0 still win where they do without it.  Not reached: products gemm_split16_serves refuses, the step-0 W_first
+ * product, the unfused recurrent path's small products, CTC, every kernel that is not a product. */
+void aslp_fp16_operands(int on);
+int aslp_fp16_operands_get(void);   /* 1 / 0: what is in force */
 void aslp_gru_forward1(float *y_cur, const float *y_prev, int ld, int S, int H);
 void aslp_gru_forward2(float *y_cur, const float *y_prev, int ld, int S, int H);
 void aslp_gru_backward1(float *d_cur, const float *d_next, const float *y_cur, const float *y_next, int ld, int S, int H);

@@ -70,6 +70,12 @@ class StepH(C.Structure):
     _fields_ = [("step", Step), ("w_hi", C.c_void_p * 2), ("w_lo", C.c_void_p * 2), ("w_slot", C.c_void_p * 2), ("ldp", C.c_int)]
 
 
+class GruStepH(C.Structure):
+    """aslp_gru_step_h (include/aslp_kernels.h)"""
+    _fields_ = [("zr_hi", C.c_void_p), ("zr_lo", C.c_void_p), ("zr_slot", C.c_void_p), ("mg_hi", C.c_void_p), ("mg_lo", C.c_void_p),
+                ("mg_slot", C.c_void_p), ("ldp_zr", C.c_int), ("ldp_mg", C.c_int)]
+
+
 class RnnVecGrad(C.Structure):
     """aslp_rnn_vec_grad (include/aslp_kernels.h)"""
     _fields_ = [("d", C.c_void_p), ("x", C.c_void_p), ("ldx", C.c_int), ("n", C.c_int), ("corr", C.c_void_p), ("param", C.c_void_p)]
@@ -213,6 +219,13 @@ _sig("aslp_lstm_step_split16_get", _i)
 _sig("aslp_lstm_step_forward_h", None, C.POINTER(StepH))
 _sig("aslp_lstm_step_backward_h", None, C.POINTER(StepH))
 _sig("aslp_lstm_step_last_pieces", _i)
+_sig("aslp_gru_step_pieces", None, _i)
+_sig("aslp_gru_step_pieces_get", _i)
+_sig("aslp_gru_step_last_pieces", _i)
+_sig("aslp_gru_step_forward_h", None, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, C.POINTER(GruStepH))
+_sig("aslp_gru_step_backward_h", None, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, C.POINTER(GruStepH))
+_sig("aslp_fp16_operands", None, _i)
+_sig("aslp_fp16_operands_get", _i)
 _sig("aslp_region_profile", None, _i)
 _sig("aslp_region_reset", None)
 _sig("aslp_region_get", C.c_long, C.c_char_p, C.POINTER(C.c_double))

@@ -356,8 +356,10 @@ bool gemm_split16_enabled() {
 
 // planes the products read per operand: 2 (default) or 1 = the hi planes alone (ASLP_GEMM_PLANES, aslp_gemm_operand_planes)
 int gemm_operand_planes() {
-  static const int env = [] { const char *e = getenv("ASLP_GEMM_PLANES"); return e != nullptr && atoi(e) == 1 ? 1 : 2; }();
-  return g_operand_planes_override > 0 ? g_operand_planes_override : env;
+  static const int env = [] { const char *e = getenv("ASLP_GEMM_PLANES"); return e == nullptr ? 0 : atoi(e); }();   // 1 or 2 count as a choice
+  if (g_operand_planes_override > 0) return g_operand_planes_override;
+  if (env == 1 || env == 2) return env;
+  return fp16_operands_on() ? 1 : 2;
 }
 
 int s16_plane_ld(int cols) {

@@ -346,8 +346,13 @@ bool step_planes_ok(const aslp_lstm_step_h *a, int K, int np, const char *who) {
 // split-fp16 products on this path: opt-in (aslp_lstm_step_split16 / ASLP_LSTM_STEP_SPLIT_F16=1)
 int g_step_split_override = -1;   // -1 = the environment decides
 bool step_split_on() {
-  static const bool env = getenv("ASLP_LSTM_STEP_SPLIT_F16") != nullptr && getenv("ASLP_LSTM_STEP_SPLIT_F16")[0] == '1' && getenv("ASLP_LSTM_STEP_SPLIT_F16")[1] == 0;
-  return g_step_split_override >= 0 ? g_step_split_override != 0 : env;
+  static const int env = [] {   // "1" or "0" count as a choice
+    const char *e = getenv("ASLP_LSTM_STEP_SPLIT_F16");
+    return (e != nullptr && (e[0] == '0' || e[0] == '1') && e[1] == 0) ? e[0] - '0' : -1;
+  }();
+  if (g_step_split_override >= 0) return g_step_split_override != 0;
+  if (env >= 0) return env != 0;
+  return fp16_operands_on();
 }
 thread_local int t_step_last_pieces = 0;   // aslp_lstm_step_last_pieces()
 

@@ -1784,8 +1784,13 @@ bool split_f16_on() {   // default on; ASLP_LSTM_SPLIT_F16=0 puts the recurrent 
 // aslp_lstm_operand_pieces(1)).  Independent of ASLP_GEMM_PLANES; without the fp16 kernels (split_f16_on() false) it has no effect.
 int g_lstm_pieces_override = -1;   // aslp_lstm_operand_pieces(): -1 = the environment decides
 int lstm_pieces() {
-  static const int env = (getenv("ASLP_LSTM_PIECES") != nullptr && getenv("ASLP_LSTM_PIECES")[0] == '1' && getenv("ASLP_LSTM_PIECES")[1] == 0) ? 1 : 2;
-  return g_lstm_pieces_override > 0 ? g_lstm_pieces_override : env;
+  static const int env = [] {   // "1" or "2" count as a choice
+    const char *e = getenv("ASLP_LSTM_PIECES");
+    return (e != nullptr && (e[0] == '1' || e[0] == '2') && e[1] == 0) ? e[0] - '0' : 0;
+  }();
+  if (g_lstm_pieces_override > 0) return g_lstm_pieces_override;
+  if (env > 0) return env;
+  return fp16_operands_on() ? 1 : 2;
 }
 template <int NP, bool FAST>
 SeqKernel pick_fwd_h_act(bool cifg, int C) {
@@ -1811,7 +1816,8 @@ SeqKernelB pick_bwd(bool cifg, int C) {
 
 typedef void (*GruKernel)(aslp_gru_seq, SeqStatus, unsigned *);
 // NP of gru_seq_fwd / gru_seq_bwd: 0 = the fp32 instruction (the default), 1 / 2 = fp16 pieces per operand (ASLP_GRU_SEQ_PIECES,
-// aslp_gru_seq_pieces()).  Independent of every LSTM and GEMM switch, and none of those reaches the GRU kernels.
+// aslp_gru_seq_pieces()).  Independent of every LSTM and GEMM switch, and none of those reaches the GRU kernels; the umbrella
+// (aslp_fp16_operands) leaves it at 0 too: the fp16 form is slower here.
 int g_gru_pieces_override = -1;   // aslp_gru_seq_pieces(): -1 = the environment decides
 int gru_pieces() {
   static const int env = [] {

@@ -254,9 +254,18 @@ RegionScope::~RegionScope() {
   r.pending.emplace_back(static_cast<hipEvent_t>(e0_), e1);
 }
 
+static int g_fp16_operands_override = -1;   // aslp_fp16_operands(): -1 = ASLP_FP16_OPERANDS decides
+bool fp16_operands_on() {
+  static const bool env = [] { const char *e = getenv("ASLP_FP16_OPERANDS"); return e != nullptr && e[0] == '1' && e[1] == 0; }();
+  return g_fp16_operands_override >= 0 ? g_fp16_operands_override != 0 : env;
+}
+
 }  // namespace aslp
 
 extern "C" {
+
+void aslp_fp16_operands(int on) { aslp::g_fp16_operands_override = on < 0 ? -1 : (on != 0); }
+int aslp_fp16_operands_get(void) { return aslp::fp16_operands_on() ? 1 : 0; }
 
 void aslp_region_profile(int enable) {
   std::lock_guard<std::mutex> lk(aslp::g_region_mu);

@@ -54,6 +54,8 @@ void CuDevice::SelectGpuId(const std::string &use_gpu) {
   if (best < 0) ASLP_ERR << "Error acquiring GPU.";
   if (hipSetDevice(best) != hipSuccess) ASLP_ERR << "hipSetDevice(" << best << ") failed";
   ASLP_LOG << "Selected device: " << best << " (automatically)";
+  if (aslp_fp16_operands_get() != 0)
+    ASLP_LOG << "fp16 operands on (ASLP_FP16_OPERANDS): one-piece layer products, LSTM recurrences and per-timestep GRU recurrences unless a site's own switch says otherwise";
   FinalizeActiveGpu();
 }
 

@@ -1077,6 +1077,16 @@ void GruStreams::ResetLstmStreams(const std::vector<int32> &stream_reset_flag) {
     if (stream_reset_flag[s] == 1) prev_state_.RowRange(s, 1).SetZero();
 }
 
+// the planes of the two matrices one pass of the per-timestep path multiplies with, in one multi-matrix conversion
+static bool GruStepPlanesOf(const CuMatrixBase &zr, const CuMatrixBase &mg, PlaneSet *pzr, PlaneSet *pmg, aslp_gru_step_h *out) {
+  PlaneSet::ConvertSpec sp[2] = {Spec(pzr, zr), Spec(pmg, mg)};
+  if (!PlaneSet::ConvertMany(sp, 2)) return false;
+  const S16View a = pzr->View(), b = pmg->View();
+  out->zr_hi = a.hi; out->zr_lo = a.lo; out->zr_slot = a.slot; out->ldp_zr = a.ld;
+  out->mg_hi = b.hi; out->mg_lo = b.lo; out->mg_slot = b.slot; out->ldp_mg = b.ld;
+  return true;
+}
+
 void GruStreams::PropagateFnc(const CuMatrixBase &in, CuMatrixBase *out) {  // :238-321
   const int H = output_dim_;
   if (nstream_ == 0) {
@@ -1121,8 +1131,19 @@ void GruStreams::PropagateFnc(const CuMatrixBase &in, CuMatrixBase *out) {  // :
   }
   const bool fused = !persistent && !unfused && aslp_gru_step_supported(H);
   t_last_path[0] = persistent ? kRecurrentPersistent : fused ? kRecurrentStepFused : kRecurrentUnfused;
-  for (int t = 1; t <= T && fused; t++)
-    aslp_gru_step_forward(buf_.RowData(t * S), buf_.RowData((t - 1) * S), w_zr_h_.Data(), w_zr_h_.Stride(), w_m_g_.Data(), w_m_g_.Stride(), ld, S, H);
+  if (fused) {
+    // opt-in (aslp_gru_step_pieces): the two products on the fp16 instruction from the planes of W_zr_h and W_m_g, made here once per pass
+    RegionScope timed("gru_recurrence_fwd");   // the conversion is part of what the mode costs
+    aslp_gru_step_h ph = aslp_gru_step_h();
+    const bool pieces = aslp_gru_step_pieces_get() != 0 && GruStepPlanesOf(w_zr_h_, w_m_g_, &step_planes_.get()->zr, &step_planes_.get()->mg, &ph);
+    for (int t = 1; t <= T; t++) {
+      if (pieces)
+        aslp_gru_step_forward_h(buf_.RowData(t * S), buf_.RowData((t - 1) * S), w_zr_h_.Data(), w_zr_h_.Stride(), w_m_g_.Data(), w_m_g_.Stride(), ld,
+                                S, H, &ph);
+      else
+        aslp_gru_step_forward(buf_.RowData(t * S), buf_.RowData((t - 1) * S), w_zr_h_.Data(), w_zr_h_.Stride(), w_m_g_.Data(), w_m_g_.Stride(), ld, S, H);
+    }
+  }
   for (int t = 1; t <= T && !fused && !persistent; t++) {
     CuSubMatrix y_zr(buf_, t * S, S, 0, 2 * H), h_prev(buf_, (t - 1) * S, S, 4 * H, H);
     y_zr.AddMatMat(1.0, h_prev, kNoTrans, w_zr_h_, kTrans, 1.0);
@@ -1174,9 +1195,17 @@ void GruStreams::BackpropagateFnc(const CuMatrixBase &in, const CuMatrixBase &, 
     }
   }
   if (fused) {
-    for (int t = T; t >= 1; t--)
-      aslp_gru_step_backward(dbuf_.RowData(t * S), dbuf_.RowData((t + 1) * S), buf_.RowData(t * S), buf_.RowData((t + 1) * S),
-                             buf_.RowData((t - 1) * S), w_zr_h_t_.Data(), w_zr_h_t_.Stride(), w_m_g_t_.Data(), w_m_g_t_.Stride(), ld, S, H, t < T);
+    RegionScope timed("gru_recurrence_bwd");   // the conversion is part of what the mode costs
+    aslp_gru_step_h ph = aslp_gru_step_h();   // as in PropagateFnc, with the planes of the transposes just made
+    const bool pieces = aslp_gru_step_pieces_get() != 0 && GruStepPlanesOf(w_zr_h_t_, w_m_g_t_, &step_planes_.get()->zr_t, &step_planes_.get()->mg_t, &ph);
+    for (int t = T; t >= 1; t--) {
+      if (pieces)
+        aslp_gru_step_backward_h(dbuf_.RowData(t * S), dbuf_.RowData((t + 1) * S), buf_.RowData(t * S), buf_.RowData((t + 1) * S),
+                                 buf_.RowData((t - 1) * S), w_zr_h_t_.Data(), w_zr_h_t_.Stride(), w_m_g_t_.Data(), w_m_g_t_.Stride(), ld, S, H, t < T, &ph);
+      else
+        aslp_gru_step_backward(dbuf_.RowData(t * S), dbuf_.RowData((t + 1) * S), buf_.RowData(t * S), buf_.RowData((t + 1) * S),
+                               buf_.RowData((t - 1) * S), w_zr_h_t_.Data(), w_zr_h_t_.Stride(), w_m_g_t_.Data(), w_m_g_t_.Stride(), ld, S, H, t < T);
+    }
   }
   for (int t = T; t >= 1 && !fused && !persistent; t--) {
     if (t < T) {

@@ -254,6 +254,19 @@ ASLP_LSTM_CLASS(BLstmProjectedStreamsLC, kBLstmProjectedStreamsLC, true, true, f
 ASLP_LSTM_CLASS(LstmCifgProjectedStreams, kLstmCifgProjectedStreams, false, true, true, false, true, true, true);
 #undef ASLP_LSTM_CLASS
 
+// fp16 planes of the two recurrent matrices of a GruStreams layer and of their transposes, for the fp16-piece products of the per-timestep
+// path (aslp_gru_step_pieces): re-made at the top of every pass that reads them, so there is no validity to track
+struct GruStepPlanes {
+  PlaneSet zr, mg, zr_t, mg_t;
+};
+struct GruStepPlanesHolder {   // a copied component starts without planes
+  GruStepPlanesHolder() = default;
+  GruStepPlanesHolder(const GruStepPlanesHolder &) {}
+  GruStepPlanesHolder &operator=(const GruStepPlanesHolder &) { return *this; }
+  GruStepPlanes *get() { if (!p) p.reset(new GruStepPlanes()); return p.get(); }
+  std::unique_ptr<GruStepPlanes> p;
+};
+
 // GruStreams (nnet-gru-streams.h:39-482)
 class GruStreams : public RecurrentBase {
  public:
@@ -284,6 +297,7 @@ class GruStreams : public RecurrentBase {
   CuVector bias_, bias_corr_;
   CuMatrix buf_, dbuf_;
   CuMatrix w_zr_h_t_, w_m_g_t_;  // transposed recurrent matrices for the fused backward step
+  GruStepPlanesHolder step_planes_;
 };
 
 }  // namespace aslp

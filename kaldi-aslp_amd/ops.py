@@ -123,6 +123,46 @@ def lstm_step_split16(on):
         lib.aslp_lstm_step_split16(before)
 
 
+def set_gru_step_pieces(n):
+    """fp16 pieces per operand of the four products of the per-timestep GRU path (aslp_gru_step_pieces): 0 = the fp32 instruction (default),
+    2 = hi and lo' on the fp16 instruction (fp32-equivalent operands), 1 = hi alone (fp16 operands, fp32 accumulation), -1 = what
+    ASLP_GRU_STEP_PIECES said"""
+    lib.aslp_gru_step_pieces(int(n))
+
+
+@contextlib.contextmanager
+def gru_step_pieces(n):
+    """per-timestep GRU recurrences inside the block multiply with n pieces per operand (0 = the fp32 instruction); the setting in force before
+    comes back on exit (pinned as an explicit setting, as gru_seq_pieces does; set_gru_step_pieces(-1) hands the choice back to the
+    environment)"""
+    before = lib.aslp_gru_step_pieces_get()
+    lib.aslp_gru_step_pieces(int(n))
+    try:
+        yield
+    finally:
+        lib.aslp_gru_step_pieces(before)
+
+
+def set_fp16_operands(on):
+    """the one switch for fp16 operands (aslp_fp16_operands): 1 = every product site that is faster with one fp16 piece per operand takes it
+    by default (layer products, persistent and per-timestep LSTM recurrences, per-timestep GRU recurrences; the persistent GRU recurrences stay
+    on the fp32 instruction), 0 = off (default),
+    -1 = what ASLP_FP16_OPERANDS said.  Every site's own setter and environment variable still wins."""
+    lib.aslp_fp16_operands(int(on))
+
+
+@contextlib.contextmanager
+def fp16_operands(on):
+    """the umbrella switch at `on` inside the block; the state in force before comes back on exit (pinned as an explicit setting;
+    set_fp16_operands(-1) hands the choice back to the environment)"""
+    before = lib.aslp_fp16_operands_get()
+    lib.aslp_fp16_operands(int(on))
+    try:
+        yield
+    finally:
+        lib.aslp_fp16_operands(before)
+
+
 class Planes:
     """the two fp16 planes of an fp32 matrix (aslp_planes_*): made once, read by every product the matrix takes part in"""
 
