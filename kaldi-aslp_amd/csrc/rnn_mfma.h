@@ -1,6 +1,11 @@
-// rnn_mfma.h -- the skinny-product building blocks shared by the fused recurrent step kernels (rnn_fused.hip,
-// gru_fused.hip): a 32 x 32 output tile (32 streams x 32 gate columns), K split over the 4 waves of a workgroup, both
-// operands K-contiguous in global memory, partial tiles combined through LDS in wave order.
+// rnn_mfma.h -- the skinny products of the fused recurrent step kernels (rnn_fused.hip, gru_fused.hip), each written once:
+// a 32 x 32 output tile (32 streams x 32 gate columns), K split into contiguous slices (one per wave, or per K-part x
+// wave), both operands K-contiguous in global memory, partial tiles combined through LDS in wave order.
+//   product_f32                  one slice on v_mfma_f32_32x32x2_f32 into the wave's partial tile
+//   product_h / product_t_h      the same on v_mfma_f32_32x32x16_f16 with operands as fp16 pieces (forward / transposed backward); called by
+//                                the GRU kernels, held inline by lstm_step_fwd_h / lstm_step_bwd_gemm_h (see there): change both
+//   tile_sum                     the waves' partial tiles, added in wave order
+//   planes_ok                    what a launch of product_h / product_t_h needs of the planes it reads (host)
 #pragma once
 #include "common.h"
 #include "split16.h"
@@ -54,6 +59,25 @@ __device__ __forceinline__ void store_tile_t(float *tile, const f32x16 &acc, int
   const int n = lane & 31, h = lane >> 5;
 #pragma unroll
   for (int e = 0; e < 16; e++) tile[n * kPad + (e & 3) + 8 * (e >> 2) + 4 * h] = acc[e];
+}
+
+// One K slice -- `part` of `nparts` contiguous runs of 8-wide K-chunks -- of a product into this wave's partial tile; !on stores zeros.
+template <int U = 8>
+__device__ __forceinline__ void product_f32(float *tile, const float *arow, const float *brow, int K, int part, int nparts,
+                                            int lane, bool on) {
+  f32x16 acc = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  const int nch = (K + 7) / 8, per = (nch + nparts - 1) / nparts;
+  if (on) mfma_k_slices<U>(acc, arow, brow, K, part * per, min(nch, (part + 1) * per), lane >> 5);
+  store_tile(tile, acc, lane);
+}
+
+// element (row, col) of the product: the NW waves' partial tiles, added in wave order (deterministic)
+template <int NW = 4>
+__device__ __forceinline__ float tile_sum(const float (*red)[32 * kPad], int row, int col) {
+  float acc = red[0][row * kPad + col];
+#pragma unroll
+  for (int w = 1; w < NW; w++) acc += red[w][row * kPad + col];
+  return acc;
 }
 
 // ---- the same products on v_mfma_f32_32x32x16_f16 with operands as fp16 pieces (csrc/split16.h: x s = hi + 2^-11 lo') ----------------
@@ -123,6 +147,54 @@ __device__ __forceinline__ void mfma_run_h(f32x16 &acc_hh, f32x16 &acc_x, const 
       }
     }
   }
+}
+
+// 16-wide k steps in flight per wave: one run of mfma_run_h, and the extent of one backward scale (128 consecutive k)
+constexpr int kRunH = 8;
+
+// One K slice -- `part` of `nparts` contiguous runs of 16-wide k steps -- of a forward product into this wave's partial tile: frow (this
+// lane's stream row of m(t-1) / h(t-1) / g(t), |value| <= 1) is split into NP pieces as it is loaded, without a scale; phi / plo are this
+// lane's gate-column row of the weight planes, scaled by the bound in *slot.  The k tail (K % 16) reads the planes' zero padding.
+template <int NP>
+__device__ __forceinline__ void product_h(float *tile, const float *frow, int K, const h16 *phi, const h16 *plo,
+                                          const unsigned *slot, int part, int nparts, int lane, bool on) {
+  const float inv_w = ldexpf(1.0f, -s16_exponent(*slot));
+  f32x16 acc = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, acx = acc;
+  const int nst = (K + 15) / 16, per = (nst + nparts - 1) / nparts, qend = min(nst, (part + 1) * per);
+  if (on)
+    for (int q0 = part * per; q0 < qend; q0 += kRunH) mfma_run_h<NP, kRunH, false, false>(acc, acx, frow, K, phi, plo, q0, qend, lane >> 5, nullptr);
+  if (NP == 2) acc += acx * (1.0f / 2048.f);
+  acc *= inv_w;
+  store_tile(tile, acc, lane);
+}
+
+// The same for a backward product, taken transposed: the planes' rows (cells of W^T) are the A operand and drow (this lane's stream row of
+// dGATES(t+1) / [d_z | d_r](t+1) / d_m(t)) is B, so a stream is a lane's COLUMN of the accumulator and its power-of-two scale -- one per
+// stream row and run of kRunH k steps, runs counted from the start of the slice, formed from the run's largest finite |value| as it is
+// loaded -- is a per-lane factor, taken out again before the run joins the slice's fp32 sum.  An all-zero run takes scale 1 and adds an
+// exact zero.
+template <int NP>
+__device__ __forceinline__ void product_t_h(float *tile, const float *drow, int K, const h16 *phi, const h16 *plo,
+                                            const unsigned *slot, int part, int nparts, int lane, bool on) {
+  const float inv_w = ldexpf(1.0f, -s16_exponent(*slot));
+  const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  f32x16 tot = zero;
+  const int nst = (K + 15) / 16, per = (nst + nparts - 1) / nparts, qend = min(nst, (part + 1) * per);
+  if (on)
+    for (int q0 = part * per; q0 < qend; q0 += kRunH) {
+      f32x16 acc = zero, acx = zero;
+      float inv_s = 1.0f;
+      mfma_run_h<NP, kRunH, true, true>(acc, acx, drow, K, phi, plo, q0, qend, lane >> 5, &inv_s);
+      if (NP == 2) acc += acx * (1.0f / 2048.f);
+      tot += acc * inv_s;
+    }
+  tot *= inv_w;
+  store_tile_t(tile, tot, lane);
+}
+
+// the planes such a launch reads: hi (lo with two pieces) 16-byte aligned, the slot present, and K rounded up to 16 halves inside a plane row
+inline bool planes_ok(const void *hi, const void *lo, const unsigned *slot, int ldp, int K, int np) {
+  return hi != nullptr && aligned16(hi) && slot != nullptr && (np == 1 || (lo != nullptr && aligned16(lo))) && (ldp & 7) == 0 && ldp >= (K + 15) / 16 * 16;
 }
 
 }  // namespace

@@ -15,7 +15,7 @@ import numpy as np
 from lstm_step_ref import errors, pow2_scale, round_pieces, sigm, weight_operand   # the split itself is the LSTM step path's
 
 WAVES = 4         # K slices of every product (kBwd1Waves is 4 too)
-RUN_STEPS = 8     # 16-wide k steps per run (kGruHU)
+RUN_STEPS = 8     # 16-wide k steps per run (kRunH)
 NAMES = ("z", "r", "m", "g", "h")
 
 

@@ -12,7 +12,7 @@ counted from the start of each of the 32 K parts (8 workgroups x 4 waves) the ba
 import numpy as np
 
 K_PARTS = 32      # kKQ x kNW of csrc/rnn_fused.hip
-RUN_STEPS = 8     # 16-wide k steps per run (kStepHU)
+RUN_STEPS = 8     # 16-wide k steps per run (kRunH)
 
 
 def gates(cifg):
