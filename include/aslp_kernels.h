@@ -361,6 +361,10 @@ void aslp_bn_backward_step_p(MatrixDim d, const float *out_diff, int od_stride, 
  * x_hat again from `in` (d.stride) and `mean` with the forward pass' own operations.  Only where this returns 1 (the
  * single-launch panel kernels: cols % 16 == 0, rows <= 1024) and all operands are 16-byte aligned. */
 int aslp_bn_panel_supported(int rows, int cols);
+/* Which kernels serve a [rows x cols] batch with 16-byte aligned operands on this device: 0 the three-launch path, 1 the single-launch
+ * panel kernels, 2 the cooperative panels (which depend on the device's CU count).  *slots (nullable): row slots per thread (4 / 8 / 16,
+ * 0 on the three-launch path); *q (nullable): workgroups per column panel (cooperative: 2..4, else 1 / 0).  Host only: launches nothing. */
+int aslp_bn_path(int rows, int cols, int *q, int *slots);
 void aslp_bn_apply(const float *in, MatrixDim d, float *out, int out_stride, const float *mean, const float *inv_std,
                    const float *scale, const float *shift);
 /* Xent::Eval (nnet-loss.cc:63-122) in one pass over [rows x cols]:

@@ -245,6 +245,7 @@ _sig("aslp_bn_backward_act", None, _vp, _md, _vp, _i, _vp, _i, _vp, _vp, _vp, _v
 _sig("aslp_bn_backward_step", None, _md, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _f, _f, _vp, _i, _vp, _i, _vp, _vp)
 _sig("aslp_bn_backward_step_p", None, _md, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _f, _f, _vp, _i, _vp, _i, _vp, _vp, C.POINTER(PlanesOut))
 _sig("aslp_bn_panel_supported", _i, _i, _i)
+_sig("aslp_bn_path", _i, _i, _i, C.POINTER(C.c_int), C.POINTER(C.c_int))
 _sig("aslp_softmax_xent_supported", _i, _i)
 _sig("aslp_xent_eval_p", _i, _vp, _md, _vp, _vp, _vp, _i, _vp, _i, C.POINTER(PlanesOut))
 _sig("aslp_xent_eval_rows", _i, _vp, _md, _vp, _vp, _vp, _i, _vp, _i, C.POINTER(PlanesOut))
