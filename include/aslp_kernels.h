@@ -679,6 +679,9 @@ void aslp_gru_backward2(float *d_cur, const float *y_cur, const float *y_prev, i
  *   coef_grad (:213-219, 251-254): coef_corr[i] = clip(sum_t in[t + i - past] .* out_diff[t])  (overwrites) */
 void aslp_fsmn_filter(float *out, int ldo, const float *src, int lds, const float *coef, int ldc, int D, int past, int future, int T,
                       int reverse);
+/* what aslp_fsmn_filter (backward == 0: 1 the LDS-tiled kernel, 0 the plain one) and aslp_fsmn_backward (backward != 0: 1 fused, 0 the separate
+ * kernels) pick when every matrix has the leading dimension ld; no launch */
+int aslp_fsmn_path(int D, int past, int future, int T, int ld, int backward);
 void aslp_fsmn_coef_grad(float *coef_corr, int ldc, const float *in, int ldi, const float *out_diff, int ldod, int D, int past, int future,
                          int T, float clip);
 /* The whole backward pass (BackpropagateFnc :204-256 + Update :258-262) in two launches: in_diff as reverse = 1 above and the tap
@@ -692,6 +695,9 @@ void aslp_fsmn_backward(float *in_diff, int ldid, float *coef_corr, int ldcc, fl
  *   wgrad   : w_diff[d][k] = sum_{s, t < L_s} in[min(t + k, L_s - 1)][d] * out_diff[t][d]  (overwrites) */
 void aslp_rowconv_forward(float *out, int ldo, const float *in, int ldi, const float *w, int D, int K, int T, int S,
                           const int32_cuda *seq_len);
+/* the ring length (4, 8, 16, 21, 32) of the streaming kernels that aslp_rowconv_forward (a = out, b = in, c = NULL / ld_c = 0) and
+ * aslp_rowconv_backward_fused (a = in_diff, b = in, c = out_diff) pick for these operands, 0 for the plain kernels; no launch */
+int aslp_rowconv_path(int D, int K, int ld_a, int ld_b, int ld_c, const void *a, const void *b, const void *c);
 void aslp_rowconv_backward(float *in_diff, int ldid, const float *out_diff, int ldod, const float *w, int D, int K, int T, int S,
                            const int32_cuda *seq_len);
 void aslp_rowconv_wgrad(float *w_diff, const float *in, int ldi, const float *out_diff, int ldod, int D, int K, int T, int S,

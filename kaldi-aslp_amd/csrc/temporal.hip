@@ -601,14 +601,31 @@ extern "C" {
 // LDS budget of the tiled CompactFsmn kernels (of the CU's 160 KB): rows of 64 floats
 static constexpr int kFsmnLdsRows = 512;   // 128 KB
 static bool fsmn_fits32(long rows, long ld) { return rows * ld < (1L << 30); }   // element offsets of the tiled kernels are 32-bit
+// LDS rows of the tiled forward (source rows + taps) and of the fused backward (od rows + in rows + taps) at C taps
+static int fsmn_forward_lds_rows(int C) { return kFsmnFrames + C - 1 + kFsmnSpare + C + kFsmnSpare; }
+static int fsmn_backward_lds_rows(int C) { return 2 * (kFsmnFrames + C - 1 + kFsmnSpare) + C + kFsmnSpare; }
+// the tiled forward serves C <= 216 taps, the fused backward C <= 126; both need 32-bit element offsets
+static bool fsmn_forward_tiled(int C, int T, int ldo, int lds, int ldc) {
+  return fsmn_forward_lds_rows(C) <= kFsmnLdsRows && fsmn_fits32(T, lds) && fsmn_fits32(T, ldo) && fsmn_fits32(C, ldc);
+}
+static bool fsmn_backward_is_fused(int D, int C, int T, int ldid, int ldc, int ldi, int ldod) {
+  const int nchunks = (T + kFsmnFrames - 1) / kFsmnFrames;
+  return fsmn_backward_lds_rows(C) <= kFsmnLdsRows && fsmn_fits32(T, ldi) && fsmn_fits32(T, ldod) && fsmn_fits32(T, ldid) && fsmn_fits32(C, ldc) &&
+         fsmn_fits32((long)nchunks * C, D);
+}
+// what aslp_fsmn_filter (backward == 0: 1 tiled, 0 plain) and aslp_fsmn_backward (backward != 0: 1 fused, 0 the separate kernels) pick for
+// matrices that all have the leading dimension ld, without a launch (tests name their path by it)
+int aslp_fsmn_path(int D, int past, int future, int T, int ld, int backward) {
+  const int C = past + future + 1;
+  return backward ? fsmn_backward_is_fused(D, C, T, ld, ld, ld, ld) : fsmn_forward_tiled(C, T, ld, ld, ld);
+}
 
 void aslp_fsmn_filter(float *out, int ldo, const float *src, int lds, const float *coef, int ldc, int D, int past, int future, int T,
                       int reverse) {
   if (T <= 0 || D <= 0) return;
   const int C = past + future + 1, pad = reverse ? future : past;
-  const int rows = kFsmnFrames + C - 1 + kFsmnSpare + C + kFsmnSpare;
-  if (rows <= kFsmnLdsRows && fsmn_fits32(T, lds) && fsmn_fits32(T, ldo) && fsmn_fits32(C, ldc)) {
-    const size_t lds_bytes = sizeof(float) * (size_t)rows * kWave;
+  if (fsmn_forward_tiled(C, T, ldo, lds, ldc)) {
+    const size_t lds_bytes = sizeof(float) * (size_t)fsmn_forward_lds_rows(C) * kWave;
     static bool attr_set = false;
     if (!attr_set) {
       ASLP_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(fsmn_filter_lds), hipFuncAttributeMaxDynamicSharedMemorySize, kFsmnLdsRows * kWave * sizeof(float)));
@@ -626,11 +643,10 @@ void aslp_fsmn_filter(float *out, int ldo, const float *src, int lds, const floa
 void aslp_fsmn_backward(float *in_diff, int ldid, float *coef_corr, int ldcc, float *coef, int ldc, const float *in, int ldi, const float *out_diff,
                         int ldod, int D, int past, int future, int T, float clip, float lr) {
   if (T <= 0 || D <= 0) return;
-  const int C = past + future + 1, ctiles = (D + kWave - 1) / kWave, rows = kFsmnFrames + C - 1;
+  const int C = past + future + 1, ctiles = (D + kWave - 1) / kWave;
   const int nchunks = (T + kFsmnFrames - 1) / kFsmnFrames;
-  const int lds_rows = 2 * (rows + kFsmnSpare) + C + kFsmnSpare;
-  if (lds_rows > kFsmnLdsRows || !fsmn_fits32(T, ldi) || !fsmn_fits32(T, ldod) || !fsmn_fits32(T, ldid) || !fsmn_fits32(C, ldc) ||
-      !fsmn_fits32((long)nchunks * C, D)) {   // a filter too long for the tile (or offsets beyond 32 bits): the separate kernels
+  const int lds_rows = fsmn_backward_lds_rows(C);
+  if (!fsmn_backward_is_fused(D, C, T, ldid, ldc, ldi, ldod)) {   // a filter too long for the tile (or offsets beyond 32 bits): the separate kernels
     aslp_fsmn_coef_grad(coef_corr, ldcc, in, ldi, out_diff, ldod, D, past, future, T, clip);
     aslp_fsmn_filter(in_diff, ldid, out_diff, ldod, coef, ldc, D, past, future, T, 1);
     if (lr != 0.0f) {   // coef += -lr coef_corr
@@ -668,24 +684,38 @@ void aslp_fsmn_coef_grad(float *coef_corr, int ldc, const float *in, int ldi, co
 }
 
 // the streaming RowConvolution kernels serve up to 32 taps on even widths with 8-byte aligned rows
-static bool rowconv_stream_serves(int D, int K, int ld_a, int ld_b, const void *a, const void *b) {
-  return K + 1 <= 32 && !(D & 1) && !(ld_a & 1) && !(ld_b & 1) && !(reinterpret_cast<uintptr_t>(a) & 7u) && !(reinterpret_cast<uintptr_t>(b) & 7u);
+// ring length of the streaming kernels at K + 1 taps (the instantiation <ring, ring == K + 1 && ring == 21>); 0: more taps than they serve
+static int rowconv_ring(int K) {
+  return K + 1 == 21 ? 21   // FutureContext 20 (the recipes' value): no tap is tested
+         : K + 1 <= 4 ? 4 : K + 1 <= 8 ? 8 : K + 1 <= 16 ? 16 : K + 1 <= 32 ? 32 : 0;
+}
+// (the forward has two matrices: ld_c = 0, c = nullptr)
+static bool rowconv_stream_serves(int D, int K, int ld_a, int ld_b, int ld_c, const void *a, const void *b, const void *c) {
+  return rowconv_ring(K) != 0 && !(D & 1) && !(ld_a & 1) && !(ld_b & 1) && !(ld_c & 1) && !(reinterpret_cast<uintptr_t>(a) & 7u) &&
+         !(reinterpret_cast<uintptr_t>(b) & 7u) && !(reinterpret_cast<uintptr_t>(c) & 7u);
+}
+// the ring length aslp_rowconv_forward (out, in) / aslp_rowconv_backward_fused (in_diff, in, out_diff) pick for these operands, 0 for the
+// plain kernels, without a launch (tests name their instantiation by it)
+int aslp_rowconv_path(int D, int K, int ld_a, int ld_b, int ld_c, const void *a, const void *b, const void *c) {
+  return rowconv_stream_serves(D, K, ld_a, ld_b, ld_c, a, b, c) ? rowconv_ring(K) : 0;
 }
 static constexpr int kRcChunk = 64;   // frames per chunk: the K halo rows cost (64 + K) / 64 of the reads
 
 void aslp_rowconv_forward(float *out, int ldo, const float *in, int ldi, const float *w, int D, int K, int T, int S,
                           const int32_cuda *seq_len) {
   if (T <= 0 || D <= 0 || S <= 0) return;
-  if (rowconv_stream_serves(D, K, ldo, ldi, out, in)) {
+  if (rowconv_stream_serves(D, K, ldo, ldi, 0, out, in, nullptr)) {
     const int dtiles = (D + kRcCols - 1) / kRcCols, sgroups = (S + kRcStreams - 1) / kRcStreams, nstrips = dtiles * sgroups;
     const int tc = kRcChunk, nchunks = (T + tc - 1) / tc;
     const dim3 grid(8 * ((nstrips + 7) / 8) * nchunks), block(kWave, kRcStreams);
 #define ASLP_RC_FWD(KP, EXACT) hipLaunchKernelGGL((rowconv_fwd_stream<KP, EXACT>), grid, block, 0, cur_stream(), out, ldo, in, ldi, w, D, K, T, S, seq_len, tc, nchunks, dtiles, nstrips)
-    if (K + 1 == 21) ASLP_RC_FWD(21, true);        // FutureContext 20 (the recipes' value): no tap is tested
-    else if (K + 1 <= 4) ASLP_RC_FWD(4, false);
-    else if (K + 1 <= 8) ASLP_RC_FWD(8, false);
-    else if (K + 1 <= 16) ASLP_RC_FWD(16, false);
-    else ASLP_RC_FWD(32, false);
+    switch (rowconv_ring(K)) {
+      case 21: ASLP_RC_FWD(21, true); break;
+      case 4: ASLP_RC_FWD(4, false); break;
+      case 8: ASLP_RC_FWD(8, false); break;
+      case 16: ASLP_RC_FWD(16, false); break;
+      default: ASLP_RC_FWD(32, false);
+    }
 #undef ASLP_RC_FWD
     check_launch("aslp_rowconv_forward");
     return;
@@ -699,7 +729,7 @@ void aslp_rowconv_backward_fused(float *in_diff, int ldid, float *w_diff, const 
                                  int K, int T, int S, const int32_cuda *seq_len, float *w_corr, float momentum, float learn_rate, int update) {
   if (T <= 0 || D <= 0 || S <= 0) return;
   if (update && !w_corr) { set_error("aslp_rowconv_backward_fused: update without w_corr"); return; }
-  if (!(rowconv_stream_serves(D, K, ldid, ldi, in_diff, in) && !(ldod & 1) && !(reinterpret_cast<uintptr_t>(out_diff) & 7u))) {
+  if (!rowconv_stream_serves(D, K, ldid, ldi, ldod, in_diff, in, out_diff)) {
     aslp_rowconv_backward(in_diff, ldid, out_diff, ldod, w, D, K, T, S, seq_len);
     aslp_rowconv_wgrad(w_diff, in, ldi, out_diff, ldod, D, K, T, S, seq_len);
     if (update) {   // nnet-row-convolution.cc:178-186
@@ -716,11 +746,13 @@ void aslp_rowconv_backward_fused(float *in_diff, int ldid, float *w_diff, const 
   if (!partial) { set_error("aslp_rowconv_backward_fused: no scratch for the tap-gradient partials -- nothing was launched (no in_diff, no gradient, no step)"); return; }
   const dim3 grid(8 * ((nstrips + 7) / 8) * nchunks), block(kWave, kRcStreams);
 #define ASLP_RC_BWD(KP, EXACT) hipLaunchKernelGGL((rowconv_bwd_fused<KP, EXACT>), grid, block, 0, cur_stream(), in_diff, ldid, partial, in, ldi, out_diff, ldod, w, D, K, T, S, seq_len, tc, nchunks, dtiles, nstrips, sgroups)
-  if (K + 1 == 21) ASLP_RC_BWD(21, true);
-  else if (K + 1 <= 4) ASLP_RC_BWD(4, false);
-  else if (K + 1 <= 8) ASLP_RC_BWD(8, false);
-  else if (K + 1 <= 16) ASLP_RC_BWD(16, false);
-  else ASLP_RC_BWD(32, false);
+  switch (rowconv_ring(K)) {
+    case 21: ASLP_RC_BWD(21, true); break;
+    case 4: ASLP_RC_BWD(4, false); break;
+    case 8: ASLP_RC_BWD(8, false); break;
+    case 16: ASLP_RC_BWD(16, false); break;
+    default: ASLP_RC_BWD(32, false);
+  }
 #undef ASLP_RC_BWD
   hipLaunchKernelGGL(rowconv_wgrad_finish, dim3((D + kWave - 1) / kWave, K + 1), dim3(kWave, kFinishWaves), 0, cur_stream(), w_diff, partial, D, K, nparts,
                      w_corr, w, momentum, learn_rate, update);

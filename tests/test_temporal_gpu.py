@@ -12,7 +12,7 @@ TOL = 1e-4
 
 
 # K + 1 taps select the instantiation of the streaming kernels (temporal.hip rowconv_fwd_stream / rowconv_bwd_fused <ring length, exact>):
-# K = 2 -> <4>, 3 and 5 -> <8>, 12 and 15 -> <16>, 20 (cfg5's FutureContext, at its full size D=512 / T=800 / S=32) -> <21, exact>, 31 -> <32>;
+# K = 2 and 3 -> <4>, 5 -> <8>, 12 and 15 -> <16>, 20 (cfg5's FutureContext, at its full size D=512 / T=800 / S=32) -> <21, exact>, 31 -> <32>;
 # an odd width (33) and more than 32 taps (40, 63, 64, 100, 130: the reference has no limit on FutureContext) run on the round-1 kernels,
 # whose tap gradients go in groups of 64 taps
 @pytest.mark.parametrize("dims", [(4, 2, 6, 3), (70, 3, 21, 4), (256, 2, 50, 8), (33, 5, 9, 2), (64, 12, 40, 4), (96, 15, 33, 5),
@@ -69,6 +69,39 @@ def test_fsmn_train_steps_match_oracle(aslp, oracle, dev, tmp_path, dims):
         idf = net.Backpropagate(torch.from_numpy(od).to(dev), want_in_diff=True).cpu().numpy()
         assert oracle.rel_err(idf, idf_ref) < TOL, ("in_diff", step)
         assert oracle.rel_err(net.GetParams(), m.coef.ravel()) < TOL, ("params", step)
+
+
+# C = 61 taps: the fused backward clips in fsmn_grad_finish; C = 130: the separate kernels clip in fsmn_coef_grad2 and step through add_mat.
+# nnet_io.fsmn cannot carry <ClipGradient> (the reference's Read / Write drop it), so the component comes from a proto.
+@pytest.mark.parametrize("dims", [(66, 30, 30, 70), (66, 65, 64, 70)])
+def test_fsmn_clip_gradient_applied_in_a_training_step(aslp, oracle, dev, dims):
+    import temporal_ref
+    D, P, F, T = dims
+    rng = np.random.default_rng(7)
+    x = rng.standard_normal((T, D)).astype(np.float32)
+    od = rng.standard_normal((T, D)).astype(np.float32)
+    g64 = temporal_ref.fsmn_grad(x, od, P, F)[0]
+    clip = float(np.float32(np.median(np.abs(g64))))   # half of the taps' gradients are clipped
+    net = aslp.Nnet.Init("<NnetProto>\n<CompactFsmn> <InputDim> %d <OutputDim> %d <PastContext> %d <FutureContext> %d <LearnRateCoef> 0.5 <ClipGradient> %.9g\n"
+                         "</NnetProto>\n" % (D, D, P, F, clip), seed=778)
+    before = net.GetParams().copy()
+    m = oracle.Fsmn(D, P, F, rng)
+    m.coef[:] = before.reshape(P + F + 1, D)
+    lr = 0.01
+    net.SetTrainOptions(learn_rate=lr, momentum=0.0)
+    out_ref = m.propagate(x)
+    idf_ref = m.backpropagate(x, od, clip)
+    clipped = np.abs(m.corr) == np.float32(clip)
+    assert 0.25 <= clipped.mean() <= 0.75
+    out = net.Propagate(torch.from_numpy(x).to(dev)).cpu().numpy()
+    assert oracle.rel_err(out, out_ref) < TOL
+    idf = net.Backpropagate(torch.from_numpy(od).to(dev), want_in_diff=True).cpu().numpy()
+    assert oracle.rel_err(idf, idf_ref) < TOL
+    after = net.GetParams()
+    oracle.assert_applied_gradients(before, after, lr * 0.5, [("coef", m.corr)], what="clipped corr")
+    # the clipped taps moved by lr clip and no further
+    step = np.abs(before.astype(np.float64) - after) / (lr * 0.5)
+    assert step.max() <= clip * (1 + 1e-4) + 2.0 ** -23 * np.abs(before).max() / (lr * 0.5)
 
 
 def test_fsmn_rejects_more_than_max_frames(aslp, oracle, dev, tmp_path):
