@@ -8,7 +8,7 @@
 
 Kernels are paired by demangled name (c++filt; mangled where there is none) after the renames, which are applied in order to the names of
 both files.  Per kernel: `name  text same|DIFF  descriptor same|DIFF`, text = the instructions from the kernel's label to its descriptor,
-descriptor = the whole .amdhsa_kernel block (registers, scratch, LDS, ...).  Only symbol names and .L labels are normalised.  The last line
+descriptor = the whole .amdhsa_kernel block (registers, scratch, LDS, ...).  Only symbol names, .L labels and the block names in loop comments are normalised.  The last line
 counts; exit status 1 on any DIFF or unpaired kernel.  Reads text, needs no GPU."""
 import argparse
 import re
@@ -29,7 +29,9 @@ def kernels(path):
         end = next(j for j in range(i, len(lines)) if lines[j].strip() == ".end_amdhsa_kernel")
         label = max(j for j in range(i) if lines[j].startswith(name + ":"))
         stop = next(j for j in range(label, i) if lines[j].startswith("\t.section"))
-        norm = lambda s: re.sub(r"\.L([A-Za-z_]+?)\d+(_\d+)?\b", r".L\1\2", s.replace(name, "SELF"))
+        # (.LBB12_3 -> .LBB_3; the same block named in a comment, "in Loop: Header=BB12_3", carries the function's number too: a kernel
+        # added in front of this one moves it, and with one more digit in it the blanks that align the comment behind a label)
+        norm = lambda s: re.sub(r"[ \t]+;", " ;", re.sub(r"\bBB\d+(_\d+)\b", r"BB\1", re.sub(r"\.L([A-Za-z_]+?)\d+(_\d+)?\b", r".L\1\2", s.replace(name, "SELF"))))
         out[name] = ([norm(s) for s in lines[label:stop]], [norm(s) for s in lines[i:end + 1]])
     return out
 

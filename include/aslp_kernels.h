@@ -233,7 +233,8 @@ void aslp_params_changed(void);
 /* A/B switch (ASLP_KEEP_WEIGHT_PLANES): 0 = the components convert their weights in every step instead of keeping the planes the
  * weight-gradient epilogue wrote; -1 = back to the environment's choice (default on) */
 void aslp_keep_weight_planes(int on);
-/* per-workgroup maxima of |src| into parts (256 floats): the start of the chain above */
+/* per-workgroup maxima of |src| into parts (256 floats): the start of the chain above (stride a multiple of 4, 16-byte aligned; cols a
+ * multiple of 4, or any width under aslp_gemm_split16_ragged -- no float behind a row's last column is read) */
 void aslp_absmax_parts(const float *src, MatrixDim d, float *parts);
 /* Large products of aslp_sgemm_ex on the fp16 matrix instruction with each fp32 operand carried as two fp16 pieces behind a power-of-two
  * scale of its matrix (csrc/gemm_split16.hip: 22 significant bits, fp32 accumulation; results agree with the fp32 instruction's to fp32
@@ -255,10 +256,25 @@ void aslp_gemm_split16_tile(int cfg);
  * under aslp_fp16_operands --, read once per process).  Process-wide, like aslp_gemm_split16. */
 void aslp_gemm_operand_planes(int n);
 int aslp_gemm_operand_planes_get(void);
+/* Sizes that are no multiple of 4 on those products (off by default).  As shipped the split path serves M, N >= 128, K >= 64 that are all
+ * multiples of 4; a number of pdfs such as 3421, a 39 x 11 = 429 wide input or an utterance's frame count send a product to the fp32
+ * instruction's register-staged kernel.  With the switch on only the three floors remain: the conversions (aslp_planes_convert, the
+ * engine's PlaneSet, aslp_absmax_parts, aslp_copy_mat_planes) take matrices of any width -- whole groups of four columns by 16-byte
+ * accesses, a row's last, partial group column by column, nothing behind the last column read or written -- and the product kernels, whose
+ * planes are padded to 64 with zeros either way, run unchanged (an N that is no multiple of 4 takes the element-wise epilogue, which leaves
+ * no planes / maxima of its output: aslp_gemm_last_parts() == 0 and the consumer converts).  Bases 16-byte aligned and leading dimensions
+ * multiples of 4 are still required.  Shapes whose sizes are multiples of 4 compute the same bits with the switch on or off.  on = 1 / 0
+ * is explicit, -1 hands the choice back to ASLP_GEMM_S16_RAGGED (only "1" turns it on; read once per process).  Independent of
+ * aslp_gemm_operand_planes (both plane counts work under it) and not a member of aslp_fp16_operands; aslp_gemm_split16(0) /
+ * ASLP_GEMM_SPLIT_F16=0 win as without it.  Process-wide. */
+void aslp_gemm_split16_ragged(int on);
+int aslp_gemm_split16_ragged_get(void);
 /* Prepared operands of such products: the two fp16 planes of an fp32 matrix, in the matrix' own layout (csrc/split16.h), made once and
  * read by every product the matrix takes part in (as op(A) or op(B), transposed or not).  aslp_planes_convert: one maximum pass and one
- * conversion pass over src [d.rows x d.cols] (cols and stride multiples of 4, 16-byte aligned).  The engine's components keep such
- * planes per tensor and step and let the kernels that write a tensor write its planes (nnet/nnet-basic.h). */
+ * conversion pass over src [d.rows x d.cols] (stride a multiple of 4, 16-byte aligned; cols a multiple of 4 unless
+ * aslp_gemm_split16_ragged is on, under which any width is converted -- no float behind a row's last column is read, the planes hold zeros
+ * from there on; -2 = refused).  The engine's components keep such planes per tensor and step and let the kernels that write a tensor
+ * write its planes (nnet/nnet-basic.h). */
 aslp_planes *aslp_planes_new(void);
 void aslp_planes_free(aslp_planes *p);
 int aslp_planes_convert(aslp_planes *p, const float *src, MatrixDim d);
@@ -303,6 +319,9 @@ long aslp_gemm_profile_get(int variant, double *flops, double *ms);
 /* the tile configuration that carried most of that variant's flops since the last reset: returns its number, writes a
  * description ("gemm_f32_glds 64x128x32, 8 waves, LDS-DMA, 3 stages") into buf */
 int aslp_gemm_profile_tile(int variant, char *buf, int buflen);
+/* flops of that variant carried since the last reset by tile configurations numbered tile_lo <= n < tile_hi (e.g. 0, 300: everything that
+ * did not run on a split-fp16 tile) */
+double aslp_gemm_profile_tile_flops(int variant, int tile_lo, int tile_hi);
 void aslp_gemm_profile_dump(void);   /* devtools: per-shape table of the event-timed launches, to stderr */
 /* Named region timers (HIP events on the launch stream, off by default): the engine brackets "lstm_recurrence_fwd",
  * "lstm_recurrence_bwd" (the timestep loops of the LSTM family), "gru_recurrence_fwd" / "_bwd" and "ctc_loss" (Warp-CTC / Eesen
@@ -386,8 +405,9 @@ int aslp_xent_eval_p(const float *net_out, MatrixDim d, const int32_cuda *labels
                      double *stats_dev, int softmax, const aslp_planes_out *diff_planes);
 /* dst [d] <- src (dst may be NULL) and the planes of src in one launch: the launch's workgroups find the matrix maximum among themselves,
  * store its bits to *out->slot and write out->hi / lo scaled by it -- what aslp_copy_mat + aslp_planes_convert leave, in one launch instead
- * of three.  Returns 1 (out->planes_written set) or 0 = not served (more rows than the chip holds at once, unaligned operands): nothing
- * was written, the caller copies and converts. */
+ * of three.  Returns 1 (out->planes_written set) or 0 = not served (more rows than the chip holds at once, unaligned operands, a width
+ * that is no multiple of 4 unless aslp_gemm_split16_ragged is on): nothing was written, the caller copies and converts.  At such a width
+ * the copy ends at the row's last column and the planes get zeros from there to the next multiple of 4 (inside out->ld). */
 int aslp_copy_mat_planes(float *dst, MatrixDim d, const float *src, int src_stride, aslp_planes_out *out);
 /* The same single launch also serves aslp_planes_convert and the components' own conversions where the matrices fit one resident grid;
  * aslp_coop_convert(0) sends them through the maximum pass + conversion pass again (same planes, bit for bit: tests compare the two). */
@@ -664,7 +684,8 @@ int aslp_gru_step_last_pieces(void);
  *   aslp_gemm_operand_planes 1,  aslp_lstm_operand_pieces 1,  aslp_lstm_step_split16 on,  aslp_gru_step_pieces 1,  aslp_gru_seq_pieces 0:
  * the fast mixed-precision mode, not a numerics-uniform one -- a site joins only where its one-piece form is faster than the site's default,
  * and the persistent GRU kernels measured slower with one piece than on the fp32 instruction, so they stay on it.  aslp_gemm_split16(0) / ASLP_GEMM_SPLIT_F16=0 and aslp_lstm_split16(0)
- * / ASLP_LSTM_SPLIT_F16=0 still win where they do without it.  Not reached: products gemm_split16_serves refuses, the step-0 W_first
+ * / ASLP_LSTM_SPLIT_F16=0 still win where they do without it.  Not reached: products gemm_split16_serves refuses (sizes that are no multiple of 4
+ * among them unless aslp_gemm_split16_ragged, a switch of its own and no member of this one, is on), the step-0 W_first
  * product, the unfused recurrent path's small products, CTC, every kernel that is not a product. */
 void aslp_fp16_operands(int on);
 int aslp_fp16_operands_get(void);   /* 1 / 0: what is in force */

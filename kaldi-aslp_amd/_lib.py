@@ -175,6 +175,8 @@ _sig("aslp_gemm_split16", None, _i)
 _sig("aslp_gemm_split16_tile", None, _i)
 _sig("aslp_gemm_operand_planes", None, _i)
 _sig("aslp_gemm_operand_planes_get", _i)
+_sig("aslp_gemm_split16_ragged", None, _i)
+_sig("aslp_gemm_split16_ragged_get", _i)
 _sig("aslp_planes_new", _vp)
 _sig("aslp_planes_free", None, _vp)
 _sig("aslp_planes_convert", _i, _vp, _vp, _md)
@@ -199,6 +201,7 @@ _sig("aslp_gemm_split16_plan", _i, _i, _i, _i, _i, _i, _i, C.POINTER(GemmEpilogu
 _sig("aslp_recurrent_last_path", _i, _i)   # include/aslp_nnet.h: 1 persistent, 2 one fused launch per timestep, 3 unfused
 _sig("aslp_gemm_profile_get", C.c_long, _i, C.POINTER(C.c_double), C.POINTER(C.c_double))
 _sig("aslp_gemm_profile_tile", _i, _i, C.c_char_p, _i)
+_sig("aslp_gemm_profile_tile_flops", C.c_double, _i, _i, _i)
 _sig("aslp_gemm_profile_dump", None)
 _sig("aslp_lstm_seq_polls", C.c_uint, _i)
 _sig("aslp_lstm_operand_pieces", None, _i)

@@ -939,6 +939,14 @@ void aslp_gemm_profile_dump(void) {  // devtools: per-shape table of the event-t
     }
   }
 }
+double aslp_gemm_profile_tile_flops(int variant, int tile_lo, int tile_hi) {
+  if (variant < 0 || variant > 3) return 0.0;
+  std::lock_guard<std::mutex> lk(g_prof_mu);
+  double fl = 0.0;
+  for (auto &kv : g_prof[variant].cfg_flops)
+    if (kv.first >= tile_lo && kv.first < tile_hi) fl += kv.second;
+  return fl;
+}
 int aslp_gemm_profile_tile(int variant, char *buf, int buflen) {
   if (variant < 0 || variant > 3) return 0;
   std::lock_guard<std::mutex> lk(g_prof_mu);

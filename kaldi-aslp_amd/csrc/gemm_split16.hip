@@ -26,7 +26,8 @@
 //   this file           the conversion kernels and PlaneSet, the launchers, the tile / split-K choice (s16_plan: a pure host function,
 //                       exported as aslp_gemm_split16_plan) and the one switch that instantiates the kernels
 //
-// A/B: ASLP_GEMM_SPLIT_F16=0 keeps every product on the fp32 instruction (default: on).
+// A/B: ASLP_GEMM_SPLIT_F16=0 keeps every product on the fp32 instruction (default: on).  ASLP_GEMM_S16_RAGGED=1 (default: off) also serves
+// sizes that are no multiple of 4: the product kernels are the same, the conversion kernels take their RAGGED forms (gemm_split16_ragged below).
 #include <algorithm>
 #include <atomic>
 
@@ -46,16 +47,24 @@ thread_local int t_last_parts = 0;   // per-wave maxima the calling thread's lat
 // covered by tw = 2^tw_log2 threads with 16 bytes each per pass (no division anywhere, every load of a thread independent).
 struct MaxJob { const float *p; int rows, cols, ld; float *part; };
 struct MaxJobs { MaxJob j[kS16MaxJobs]; };
+// RAGGED: some matrix of the launch has a width that is no multiple of 4 (the host chooses): the group that holds a row's last column
+// is loaded column by column (split16.h s16_load4_ragged)
+template <bool RAGGED>
 __global__ void __launch_bounds__(256) s16_absmax_kernel(MaxJobs jobs, int tw_log2) {
   const MaxJob j = jobs.j[blockIdx.y];
-  const int c4 = j.cols >> 2, tw = 1 << tw_log2, rpw = 256 >> tw_log2;
+  const int c4 = RAGGED ? (j.cols + 3) >> 2 : j.cols >> 2, tw = 1 << tw_log2, rpw = 256 >> tw_log2;
   const int tr = threadIdx.x >> tw_log2, tc = threadIdx.x & (tw - 1);
   const int per = (j.rows + gridDim.x - 1) / gridDim.x, r0 = blockIdx.x * per, r1 = min(j.rows, r0 + per);
   float m = 0.f;
   for (int r = r0 + tr; r < r1; r += rpw) {
     const float *row = j.p + (long)r * j.ld;
+    if constexpr (RAGGED) {
 #pragma unroll 4
-    for (int c = tc; c < c4; c += tw) m = s16_absmax4(m, *reinterpret_cast<const float4 *>(row + 4 * c));
+      for (int c = tc; c < c4; c += tw) m = s16_absmax4(m, s16_load4_ragged(row, 4 * c, j.cols));
+    } else {
+#pragma unroll 4
+      for (int c = tc; c < c4; c += tw) m = s16_absmax4(m, *reinterpret_cast<const float4 *>(row + 4 * c));
+    }
   }
   m = wave_max(m);
   __shared__ float wm[4];
@@ -93,6 +102,9 @@ __global__ void __launch_bounds__(256) s16_weight_bound_kernel(BoundJob j) {
 // Same dealing of rows; a thread converts 8 consecutive columns per pass (two 16-byte loads, one 16-byte store per plane).
 struct ConvJob { const float *src; int ld_src; S16View pl; const float *part; int nparts; };
 struct ConvJobs { ConvJob j[kS16MaxJobs]; };
+// RAGGED: as s16_absmax_kernel -- in both branches the 4-column group that holds a row's last column takes the masked loads, so that the
+// planes get zeros from column `cols` on and nothing from behind the matrix reaches them
+template <bool RAGGED>
 __global__ void __launch_bounds__(256) split16_convert_kernel(ConvJobs jobs, int tw_log2) {
   const ConvJob j = jobs.j[blockIdx.y];
   const int k8 = j.pl.ld >> 3, tw = 1 << tw_log2, rpw = 256 >> tw_log2;   // ld is a multiple of 64
@@ -110,8 +122,13 @@ __global__ void __launch_bounds__(256) split16_convert_kernel(ConvJobs jobs, int
       const int u = (int)threadIdx.x + i * 256, ur = u / k8, r = r0 + ur, c = u - ur * k8;
       const bool ok = u < units && r < j.pl.rows;
       const float *row = j.src + (long)r * j.ld_src;
-      a[i][0] = ok && 8 * c < j.pl.cols ? *reinterpret_cast<const float4 *>(row + 8 * c) : float4{0.f, 0.f, 0.f, 0.f};
-      a[i][1] = ok && 8 * c + 4 < j.pl.cols ? *reinterpret_cast<const float4 *>(row + 8 * c + 4) : float4{0.f, 0.f, 0.f, 0.f};
+      if constexpr (RAGGED) {
+        a[i][0] = ok && 8 * c < j.pl.cols ? s16_load4_ragged(row, 8 * c, j.pl.cols) : float4{0.f, 0.f, 0.f, 0.f};
+        a[i][1] = ok && 8 * c + 4 < j.pl.cols ? s16_load4_ragged(row, 8 * c + 4, j.pl.cols) : float4{0.f, 0.f, 0.f, 0.f};
+      } else {
+        a[i][0] = ok && 8 * c < j.pl.cols ? *reinterpret_cast<const float4 *>(row + 8 * c) : float4{0.f, 0.f, 0.f, 0.f};
+        a[i][1] = ok && 8 * c + 4 < j.pl.cols ? *reinterpret_cast<const float4 *>(row + 8 * c + 4) : float4{0.f, 0.f, 0.f, 0.f};
+      }
     }
     const unsigned mbits = __float_as_uint(reduce_parts(j.part, j.nparts));
     if (blockIdx.x == 0 && threadIdx.x == 0) *j.pl.slot = mbits;
@@ -137,8 +154,13 @@ __global__ void __launch_bounds__(256) split16_convert_kernel(ConvJobs jobs, int
 #pragma unroll 2
     for (int c = tc; c < k8; c += tw) {
       half4 h0 = {0, 0, 0, 0}, l0 = {0, 0, 0, 0}, h1 = {0, 0, 0, 0}, l1 = {0, 0, 0, 0};
-      if (row_ok && 8 * c < j.pl.cols) s16_split4(*reinterpret_cast<const float4 *>(row + 8 * c), s, &h0, &l0);          // cols % 4 == 0
-      if (row_ok && 8 * c + 4 < j.pl.cols) s16_split4(*reinterpret_cast<const float4 *>(row + 8 * c + 4), s, &h1, &l1);
+      if constexpr (RAGGED) {
+        if (row_ok && 8 * c < j.pl.cols) s16_split4(s16_load4_ragged(row, 8 * c, j.pl.cols), s, &h0, &l0);
+        if (row_ok && 8 * c + 4 < j.pl.cols) s16_split4(s16_load4_ragged(row, 8 * c + 4, j.pl.cols), s, &h1, &l1);
+      } else {
+        if (row_ok && 8 * c < j.pl.cols) s16_split4(*reinterpret_cast<const float4 *>(row + 8 * c), s, &h0, &l0);          // cols % 4 == 0
+        if (row_ok && 8 * c + 4 < j.pl.cols) s16_split4(*reinterpret_cast<const float4 *>(row + 8 * c + 4), s, &h1, &l1);
+      }
       *reinterpret_cast<half8 *>(j.pl.hi + (long)r * j.pl.ld + 8 * c) = __builtin_shufflevector(h0, h1, 0, 1, 2, 3, 4, 5, 6, 7);
       *reinterpret_cast<half8 *>(j.pl.lo + (long)r * j.pl.ld + 8 * c) = __builtin_shufflevector(l0, l1, 0, 1, 2, 3, 4, 5, 6, 7);
     }
@@ -149,6 +171,23 @@ inline int tw_log2_for(int units) {
   int l = 0;
   while (l < 8 && (1 << l) < units) l++;
   return l;
+}
+// The launches of the two kernels for the first n jobs (matrices in one launch share the threads-per-row choice: the widest one's).  The
+// ragged forms run only where a matrix of the launch has a width that is no multiple of 4; whether such a matrix may come here at all
+// (gemm_split16_ragged) is the callers' business.
+void launch_absmax(const MaxJobs &ms, int n) {
+  int c4 = 0;
+  bool ragged = false;
+  for (int i = 0; i < n; i++) { c4 = std::max(c4, (ms.j[i].cols + 3) >> 2); ragged = ragged || (ms.j[i].cols & 3); }
+  if (ragged) hipLaunchKernelGGL(s16_absmax_kernel<true>, dim3(kS16ConvParts, n), dim3(256), 0, cur_stream(), ms, tw_log2_for(c4));
+  else hipLaunchKernelGGL(s16_absmax_kernel<false>, dim3(kS16ConvParts, n), dim3(256), 0, cur_stream(), ms, tw_log2_for(c4));
+}
+void launch_convert(const ConvJobs &js, int n, int grid_x) {
+  int k8 = 0;
+  bool ragged = false;
+  for (int i = 0; i < n; i++) { k8 = std::max(k8, js.j[i].pl.ld >> 3); ragged = ragged || (js.j[i].pl.cols & 3); }
+  if (ragged) hipLaunchKernelGGL(split16_convert_kernel<true>, dim3(grid_x, n), dim3(256), 0, cur_stream(), js, tw_log2_for(k8));
+  else hipLaunchKernelGGL(split16_convert_kernel<false>, dim3(grid_x, n), dim3(256), 0, cur_stream(), js, tw_log2_for(k8));
 }
 
 // ---- launchers -----------------------------------------------------------------------------------------------------------------------
@@ -236,7 +275,11 @@ int s16_plan_tile(bool a_kc, bool b_kc, int M, int N, bool extra, long t128, lon
     // both operands reduction-major: the 128 x 128 kernel wherever its grid fills the chip about as well as the 64 x 128 one's --
     // rounds of 256 workgroups, a 128 x 128 round costing ~1.6 of a 64 x 128 one (measured on 2048 x 2048 x 1024)
     const double cost128 = tu.ks128_cost * (double)((t128 + 255) / 256), cost64 = (double)((t64 + 255) / 256);
-    if (tu.ks128 && (cfg == 0 || cfg == 328) && (cfg == 328 || (t128 >= 200 && cost128 <= cost64)) && (N % 8) == 0 && (M % 8) == 0) return 328;
+    // (M and N multiples of 8 is what the kernel was measured and shipped with, and multiples of 4 keep that condition.  Nothing in the kernel
+    // needs it -- the planes' pitch is a multiple of 64 halves, so every 16-byte piece it fetches is whole -- so an M or N that is no multiple
+    // of 4, which gets here only under gemm_split16_ragged(), is taken like a multiple of 8)
+    if (tu.ks128 && (cfg == 0 || cfg == 328) && (cfg == 328 || (t128 >= 200 && cost128 <= cost64)) && (((N % 8) == 0 && (M % 8) == 0) || ((M | N) & 3)))
+      return 328;
   }
   // 128 x 128 (cfg 311; both operands reduction-contiguous, nothing extra to leave) where its rounds of 256 workgroups cost no more than the
   // 64 x 128 tile's, a 128 x 128 round counted as two: level at 2048^3 ... 8192 x 2048 x 2048 (57.8 / 222.3 against 57.4 / 220.8 us from
@@ -346,6 +389,7 @@ void s16_launch_tile(GemmArgs &g, const S16Operands &ops, int tile, bool extra) 
 int g_split16_override = -1;   // aslp_gemm_split16(): -1 = the environment decides
 int g_split16_tile_override = -1;   // aslp_gemm_split16_tile(): -1 = ASLP_GEMM_SPLIT_F16_TILE / the heuristic
 int g_operand_planes_override = -1;   // aslp_gemm_operand_planes(): -1 = ASLP_GEMM_PLANES decides
+int g_ragged_override = -1;   // aslp_gemm_split16_ragged(): -1 = ASLP_GEMM_S16_RAGGED decides
 
 }  // namespace
 
@@ -367,8 +411,16 @@ int s16_plane_ld(int cols) {
   //  31.6 / 31.8 us)
   return (cols + kS16Pad - 1) / kS16Pad * kS16Pad;
 }
+// Sizes that are no multiple of 4 (ASLP_GEMM_S16_RAGGED=1 / aslp_gemm_split16_ragged(1); default off, only "1" turns it on): the number
+// of pdfs of a tree, 39 x 11 input widths, an utterance's frame count.  The product kernels never needed the multiple -- planes are padded
+// to 64 both ways with zeros, the K loop runs over the padded extent, the narrow epilogue masks element by element -- the conversion
+// kernels did, and have ragged forms now.  Not under the aslp_fp16_operands umbrella; works with either plane count.
+bool gemm_split16_ragged() {
+  static const bool env = [] { const char *e = getenv("ASLP_GEMM_S16_RAGGED"); return e != nullptr && e[0] == '1' && e[1] == '\0'; }();
+  return g_ragged_override >= 0 ? g_ragged_override != 0 : env;
+}
 bool gemm_split16_serves(int M, int N, int K) {
-  return gemm_split16_enabled() && M >= 128 && N >= 128 && K >= 64 && !((M | N | K) & 3);
+  return gemm_split16_enabled() && M >= 128 && N >= 128 && K >= 64 && (gemm_split16_ragged() || !((M | N | K) & 3));
 }
 static int g_keep_override = -1;
 bool s16_keep_weight_planes() {
@@ -441,17 +493,19 @@ bool PlaneSet::SetBound(float bound) {
   }
   return true;
 }
+// a width the conversions take: a multiple of 4, or any under gemm_split16_ragged() (the base and the stride stay 16-byte aligned)
+static bool s16_width_ok(int cols) { return !(cols & 3) || gemm_split16_ragged(); }
 bool PlaneSet::ConvertWithParts(const float *src, int rows, int cols, int stride, int nparts) {
-  if ((cols & 3) || (stride & 3) || !aligned16(src) || nparts > kS16MaxParts) return false;
+  if (!s16_width_ok(cols) || (stride & 3) || !aligned16(src) || nparts > kS16MaxParts) return false;
   if (!Reserve(rows, cols)) return false;
   host_bound_ = -1.f;
   ConvJobs js;
   js.j[0] = ConvJob{src, stride, View(), parts_, nparts};
-  hipLaunchKernelGGL(split16_convert_kernel, dim3(std::min(rows_p_, 512), 1), dim3(256), 0, cur_stream(), js, tw_log2_for(ld_ >> 3));
+  launch_convert(js, 1, std::min(rows_p_, 512));
   return true;
 }
 bool PlaneSet::ConvertFrom(const float *src, int rows, int cols, int stride) {
-  if ((cols & 3) || (stride & 3) || !aligned16(src)) return false;
+  if (!s16_width_ok(cols) || (stride & 3) || !aligned16(src)) return false;
   if (!Reserve(rows, cols)) return false;
   {
     const CoopConvJob job = {src, stride, nullptr, 0, View(), nullptr, 0};
@@ -459,7 +513,7 @@ bool PlaneSet::ConvertFrom(const float *src, int rows, int cols, int stride) {
   }
   MaxJobs ms;
   ms.j[0] = MaxJob{src, rows, cols, stride, parts_};
-  hipLaunchKernelGGL(s16_absmax_kernel, dim3(kS16ConvParts, 1), dim3(256), 0, cur_stream(), ms, tw_log2_for(cols >> 2));
+  launch_absmax(ms, 1);
   return ConvertWithParts(src, rows, cols, stride, kS16ConvParts);
 }
 // several matrices in one maximum launch and one conversion launch (the recurrent layers convert up to seven small tensors at a time)
@@ -468,19 +522,17 @@ bool PlaneSet::ConvertMany(const ConvertSpec *specs, int n, const SeqFillJob *fi
   if (n <= 0 || n > kS16MaxJobs) return false;
   MaxJobs ms;
   ConvJobs js;
-  int max_c4 = 0, max_k8 = 0, max_rows = 0;
+  int max_rows = 0;
   bool need_max = false;
   for (int i = 0; i < n; i++) {
     const ConvertSpec &c = specs[i];
-    if (!c.planes || !c.src || (c.cols & 3) || (c.stride & 3) || !aligned16(c.src)) return false;
+    if (!c.planes || !c.src || !s16_width_ok(c.cols) || (c.stride & 3) || !aligned16(c.src)) return false;
     if (!c.planes->Reserve(c.rows, c.cols)) return false;
     c.planes->host_bound_ = -1.f;
     const bool given = c.parts != nullptr && c.nparts > 0 && c.nparts <= kS16MaxParts;
     need_max = need_max || !given;
     ms.j[i] = MaxJob{c.src, c.rows, c.cols, c.stride, c.planes->parts_};
     js.j[i] = given ? ConvJob{c.src, c.stride, c.planes->View(), c.parts, c.nparts} : ConvJob{c.src, c.stride, c.planes->View(), c.planes->parts_, kS16ConvParts};
-    max_c4 = std::max(max_c4, c.cols >> 2);
-    max_k8 = std::max(max_k8, c.planes->ld_ >> 3);
     max_rows = std::max(max_rows, c.planes->rows_p_);
   }
   if (need_max) {   // one launch for the maxima and the planes where the matrices fit one resident grid
@@ -495,8 +547,8 @@ bool PlaneSet::ConvertMany(const ConvertSpec *specs, int n, const SeqFillJob *fi
       return true;
     }
   }
-  if (need_max) hipLaunchKernelGGL(s16_absmax_kernel, dim3(kS16ConvParts, n), dim3(256), 0, cur_stream(), ms, tw_log2_for(max_c4));
-  hipLaunchKernelGGL(split16_convert_kernel, dim3(std::min(max_rows, 512), n), dim3(256), 0, cur_stream(), js, tw_log2_for(max_k8));
+  if (need_max) launch_absmax(ms, n);
+  launch_convert(js, n, std::min(max_rows, 512));
   return true;
 }
 const float *PlaneSet::OneBound() {
@@ -617,13 +669,13 @@ bool gemm_split16_launch(GemmArgs &g, bool a_kc, bool b_kc, int cfg, const S16Vi
   ConvJobs js;
   if (!pa && !pb) {
     ms.j[0] = ma; ms.j[1] = mb; js.j[0] = ca; js.j[1] = cb;
-    hipLaunchKernelGGL(s16_absmax_kernel, dim3(kS16ConvParts, 2), dim3(256), 0, cur_stream(), ms, tw_log2_for(std::max(a_cols, b_cols) >> 2));
-    hipLaunchKernelGGL(split16_convert_kernel, dim3(512, 2), dim3(256), 0, cur_stream(), js, tw_log2_for(std::max(va.ld, vb.ld) >> 3));
+    launch_absmax(ms, 2);
+    launch_convert(js, 2, 512);
   } else {
     ms.j[0] = pa ? mb : ma;
     js.j[0] = pa ? cb : ca;
-    hipLaunchKernelGGL(s16_absmax_kernel, dim3(kS16ConvParts, 1), dim3(256), 0, cur_stream(), ms, tw_log2_for(ms.j[0].cols >> 2));
-    hipLaunchKernelGGL(split16_convert_kernel, dim3(512, 1), dim3(256), 0, cur_stream(), js, tw_log2_for(js.j[0].pl.ld >> 3));
+    launch_absmax(ms, 1);
+    launch_convert(js, 1, 512);
   }
   return gemm_split16_planes_launch(g, a_kc, b_kc, va, vb, nullptr, nullptr, cfg);
 }
@@ -667,6 +719,8 @@ void aslp_gemm_split16(int on) { aslp::g_split16_override = on < 0 ? -1 : (on !=
 void aslp_gemm_split16_tile(int cfg) { aslp::g_split16_tile_override = cfg < 0 ? -1 : cfg; }
 void aslp_gemm_operand_planes(int n) { aslp::g_operand_planes_override = (n == 1 || n == 2) ? n : -1; }
 int aslp_gemm_operand_planes_get(void) { return aslp::gemm_operand_planes(); }
+void aslp_gemm_split16_ragged(int on) { aslp::g_ragged_override = on < 0 ? -1 : (on != 0); }
+int aslp_gemm_split16_ragged_get(void) { return aslp::gemm_split16_ragged() ? 1 : 0; }
 int aslp_gemm_last_parts(void) { return aslp::gemm_split16_last_parts(); }
 void aslp_weight_bound(const float *w_parts, int n_w, const float *c_parts, int n_c, const aslp_planes *a, const aslp_planes *b, int K, float alpha,
                        float beta, float w_alpha, float clip, aslp_planes *w_planes) {
@@ -680,10 +734,10 @@ void aslp_weight_bound(const float *w_parts, int n_w, const float *c_parts, int 
 }
 void aslp_absmax_parts(const float *src, MatrixDim d, float *parts) {
   using namespace aslp;
-  if (!src || !parts || (d.cols & 3) || (d.stride & 3) || !aligned16(src)) { set_error("aslp_absmax_parts: unsupported matrix"); return; }
+  if (!src || !parts || !s16_width_ok(d.cols) || (d.stride & 3) || !aligned16(src)) { set_error("aslp_absmax_parts: unsupported matrix"); return; }
   MaxJobs ms;
   ms.j[0] = MaxJob{src, d.rows, d.cols, d.stride, parts};
-  hipLaunchKernelGGL(s16_absmax_kernel, dim3(kS16ConvParts, 1), dim3(256), 0, cur_stream(), ms, tw_log2_for(d.cols >> 2));
+  launch_absmax(ms, 1);
   check_launch("aslp_absmax_parts");
 }
 }

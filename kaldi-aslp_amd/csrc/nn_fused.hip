@@ -639,8 +639,11 @@ __device__ __forceinline__ float coop_grid_max(float wg_max, unsigned long long 
 // input -- copy + maximum pass + conversion pass were three launches in front of the first layer product -- and PlaneSet::ConvertFrom /
 // ConvertMany): a thread holds U 16-byte pieces of its matrix, the workgroups of a matrix find its maximum among themselves as above.  A
 // matrix whose bound is given (parts) takes it from there.
+// RAGGED: a matrix of the launch has a width that is no multiple of 4 (the host chooses, under gemm_split16_ragged()): a row then has one
+// more piece, the group that holds its last column -- loaded and copied column by column (split16.h s16_load4_ragged), its planes written
+// whole, with zeros from column `cols` on (inside the planes' pitch, which is a multiple of 4: zeros belong there).
 struct CoopConvJobs { CoopConvJob j[kS16MaxJobs]; };
-template <int U>
+template <int U, bool RAGGED = false>
 __global__ void __launch_bounds__(kPanelThreads) copy_planes_coop(CoopConvJobs jobs, unsigned long long *gmax, unsigned token, unsigned *err, SeqFillJob fill) {
   __shared__ float red[kPanelWaves];
   if (fill.buf0 != nullptr) {   // (uniform) a recurrent layer's buffer preparation rides along: stores only, spread over the launch's workgroups
@@ -648,7 +651,7 @@ __global__ void __launch_bounds__(kPanelThreads) copy_planes_coop(CoopConvJobs j
     for (int r = (int)(blockIdx.y * gridDim.x + blockIdx.x); r < 2 * per; r += nb) seq_fill_row(fill, r % per, r / per);
   }
   const CoopConvJob job = jobs.j[blockIdx.y];
-  const int rows = job.pl.rows, cols = job.pl.cols, c4 = cols >> 2, units = rows * c4;
+  const int rows = job.pl.rows, cols = job.pl.cols, c4 = RAGGED ? (cols + 3) >> 2 : cols >> 2, units = rows * c4;
   float4 v[U];
   int rr[U], cc[U];
   float m = 0.f;
@@ -658,7 +661,8 @@ __global__ void __launch_bounds__(kPanelThreads) copy_planes_coop(CoopConvJobs j
     const int r = u / c4;
     rr[k] = u < units ? r : -1;
     cc[k] = 4 * (u - r * c4);
-    v[k] = u < units ? *reinterpret_cast<const float4 *>(job.src + (long)r * job.ld_src + cc[k]) : make_float4(0.f, 0.f, 0.f, 0.f);
+    if constexpr (RAGGED) v[k] = u < units ? s16_load4_ragged(job.src + (long)r * job.ld_src, cc[k], cols) : make_float4(0.f, 0.f, 0.f, 0.f);
+    else v[k] = u < units ? *reinterpret_cast<const float4 *>(job.src + (long)r * job.ld_src + cc[k]) : make_float4(0.f, 0.f, 0.f, 0.f);
   }
   if (job.parts != nullptr) {   // (uniform) the bound is known: every workgroup reads it
     for (int i0 = threadIdx.x; i0 < job.nparts; i0 += 4 * kPanelThreads) {
@@ -670,7 +674,20 @@ __global__ void __launch_bounds__(kPanelThreads) copy_planes_coop(CoopConvJobs j
   }
 #pragma unroll
   for (int k = 0; k < U; k++) {
-    if (rr[k] >= 0 && job.dst != nullptr) *reinterpret_cast<float4 *>(job.dst + (long)rr[k] * job.ld_dst + cc[k]) = v[k];
+    if constexpr (RAGGED) {
+      if (rr[k] >= 0 && job.dst != nullptr) {
+        float *d = job.dst + (long)rr[k] * job.ld_dst + cc[k];
+        if (cc[k] + 4 <= cols) {
+          *reinterpret_cast<float4 *>(d) = v[k];
+        } else {   // (the copy's row ends where the source's does: nothing is written behind it)
+          d[0] = v[k].x;
+          if (cc[k] + 1 < cols) d[1] = v[k].y;
+          if (cc[k] + 2 < cols) d[2] = v[k].z;
+        }
+      }
+    } else {
+      if (rr[k] >= 0 && job.dst != nullptr) *reinterpret_cast<float4 *>(job.dst + (long)rr[k] * job.ld_dst + cc[k]) = v[k];
+    }
     if (job.parts == nullptr) m = s16_absmax4(m, v[k]);
   }
   m = wave_max(m);
@@ -1258,13 +1275,15 @@ bool coop_convert_launch(const CoopConvJob *jobs, int n, const SeqFillJob *fill)
   // would wait for workgroups the other keeps from being placed), and two launches of this thread would meet in one exchange area.
   if (off || !g_coop_convert_on || n <= 0 || n > kS16MaxJobs) return false;
   long max_units = 0;
+  bool ragged = false;   // a width that is no multiple of 4: only under gemm_split16_ragged(), on the kernel's ragged form
   CoopConvJobs js;
   for (int i = 0; i < n; i++) {
     const CoopConvJob &c = jobs[i];
-    if (!c.src || !c.pl.hi || !c.pl.lo || !c.pl.slot || c.pl.rows <= 0 || c.pl.cols <= 0 || (c.pl.cols & 3) || (c.ld_src & 3) || !aligned16(c.src) ||
-        (c.dst && ((c.ld_dst & 3) || !aligned16(c.dst))) || c.pl.ld < c.pl.cols || (c.pl.ld & 3) || (c.parts && c.nparts <= 0))
+    if (!c.src || !c.pl.hi || !c.pl.lo || !c.pl.slot || c.pl.rows <= 0 || c.pl.cols <= 0 || ((c.pl.cols & 3) && !gemm_split16_ragged()) || (c.ld_src & 3) ||
+        !aligned16(c.src) || (c.dst && ((c.ld_dst & 3) || !aligned16(c.dst))) || c.pl.ld < c.pl.cols || (c.pl.ld & 3) || (c.parts && c.nparts <= 0))
       return false;
-    max_units = std::max(max_units, (long)c.pl.rows * (c.pl.cols >> 2));
+    ragged = ragged || (c.pl.cols & 3);
+    max_units = std::max(max_units, (long)c.pl.rows * ((c.pl.cols + 3) >> 2));
     js.j[i] = c;
   }
   CoopState &st = coop_state();
@@ -1281,8 +1300,10 @@ bool coop_convert_launch(const CoopConvJob *jobs, int n, const SeqFillJob *fill)
   if (++st.token == 0) st.token = 1;
   SeqFillJob fj = {nullptr, nullptr, 0, 0, 0, 0, 0, nullptr, 0, 0};
   if (fill) fj = *fill;
-#define ASLP_COPY_PLANES(UU) hipLaunchKernelGGL((copy_planes_coop<UU>), dim3(gx, n), dim3(kPanelThreads), 0, cur_stream(), js, st.gmax, st.token, st.err, fj)
+#define ASLP_COPY_PLANES_R(UU, RG) hipLaunchKernelGGL((copy_planes_coop<UU, RG>), dim3(gx, n), dim3(kPanelThreads), 0, cur_stream(), js, st.gmax, st.token, st.err, fj)
+#define ASLP_COPY_PLANES(UU) do { if (ragged) ASLP_COPY_PLANES_R(UU, true); else ASLP_COPY_PLANES_R(UU, false); } while (0)
   if (U == 4) ASLP_COPY_PLANES(4); else if (U == 8) ASLP_COPY_PLANES(8); else ASLP_COPY_PLANES(16);
+#undef ASLP_COPY_PLANES_R
 #undef ASLP_COPY_PLANES
   check_launch("coop_convert");
   return true;

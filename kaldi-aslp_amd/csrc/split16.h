@@ -81,6 +81,18 @@ __device__ __forceinline__ float s16_absmax4(float m, const float4 v) {
   for (int i = 0; i < 4; i++) m = fmaxf(m, a[i] < 3.0e38f ? a[i] : 0.f);
   return m;
 }
+// Columns [c, c + 4) of a row of a matrix whose width `cols` is no multiple of 4 (the ragged forms of the conversion kernels): a whole
+// group by one 16-byte load, the group that holds the matrix' last column by 4-byte loads of the columns below `cols` alone, zeros
+// elsewhere.  No float at a column >= cols is read: behind it lies undefined row padding or, for a window of a wider matrix, the neighbour.
+__device__ __forceinline__ float4 s16_load4_ragged(const float *row, int c, int cols) {
+  if (c + 4 <= cols) return *reinterpret_cast<const float4 *>(row + c);
+  float4 v;
+  v.x = c < cols ? row[c] : 0.f;
+  v.y = c + 1 < cols ? row[c + 1] : 0.f;
+  v.z = c + 2 < cols ? row[c + 2] : 0.f;
+  v.w = 0.f;   // (c + 3 < cols would have been a whole group)
+  return v;
+}
 #endif
 
 // (Optional copy and) planes of up to kS16MaxJobs matrices in ONE launch, each scaled by its own maximum, which the launch's workgroups find
@@ -132,7 +144,8 @@ class PlaneSet {
   unsigned *Slot() const { return slot_; }
   int Rows() const { return rows_; }
   int Cols() const { return cols_; }
-  // max pass + conversion of src (two launches on the current stream)
+  // max pass + conversion of src (two launches on the current stream).  All conversions: src 16-byte aligned, stride a multiple of 4, cols
+  // a multiple of 4 -- or any width under gemm_split16_ragged(), on the kernels' ragged forms; false = refused, nothing launched
   bool ConvertFrom(const float *src, int rows, int cols, int stride);
   // several matrices with ONE maximum launch and ONE conversion launch (at most 8)
   // (parts / nparts: device maxima that bound |src| -- left by the kernel that wrote src, or OneBound() for values known to lie in
@@ -180,6 +193,9 @@ bool gemm_split16_enabled();
 int gemm_operand_planes();   // 2, or 1 = the products read the hi planes alone (ASLP_GEMM_PLANES / aslp_gemm_operand_planes)
 // would aslp_sgemm_ex carry an M x N x K product on the fp16 instruction (switch on, shape served)?
 bool gemm_split16_serves(int M, int N, int K);
+// are sizes that are no multiple of 4 served (ASLP_GEMM_S16_RAGGED=1 / aslp_gemm_split16_ragged; default off)?  Then the conversions
+// (PlaneSet::Convert*, coop_convert_launch, aslp_absmax_parts) take matrices of any width on their ragged forms
+bool gemm_split16_ragged();
 int gemm_split16_last_parts();
 int gemm_split16_last_tile();   // 311 / 308 / 328, one plane: 404 / 408 / 411 (gemm_split16.hip)
 void gemm_split16_reset_last_parts();

@@ -284,7 +284,10 @@ class AffineTransform : public UpdatableComponent {
     // (csrc/split16.h).  Their scale must be known before the first tile is written: a bound of max |W - lr W_corr| that every
     // workgroup forms from the maxima of |W| and |W_corr| the previous step's epilogue left (the first time: one pass over each),
     // the operands' bounds and K.
+    // (an input width that is no multiple of 4 -- served under gemm_split16_ragged() -- takes the element-wise epilogue, which leaves neither
+    // planes nor maxima: nothing to keep, the forward and in-diff products convert the weights by a launch of their own)
     const bool keep = s16_keep_weight_planes() && plain && max_norm_ <= 0.0 && !aliased_silently_ && pa && pb && gemm_split16_serves(num_frames, output_dim_, input_dim_) &&
+                      (input_dim_ & 3) == 0 &&
                       gemm_split16_max_parts(output_dim_, input_dim_) <= kS16MaxParts && w_planes_.get().Reserve(output_dim_, input_dim_);
     if (keep) {
       for (int i = 0; i < 2; i++) {

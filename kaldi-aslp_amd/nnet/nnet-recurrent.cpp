@@ -263,6 +263,7 @@ bool LstmDir::RefreshStepPlanes(const LstmDir *const *dirs, int n, bool transpos
     bool &ok = transposed ? pl->eff_t_ok : pl->eff_ok;
     if (ok) continue;
     const CuMatrixBase &w = transposed ? static_cast<const CuMatrixBase &>(dirs[d]->w_eff_t) : dirs[d]->Weff();
+    if (w.NumCols() & 3) return false;   // (the step kernels read these planes 16 bytes at a time: no ragged widths here, whatever gemm_split16_ragged() says)
     sp[m] = PlaneSet::ConvertSpec{transposed ? &pl->eff_t : &pl->eff, w.Data(), w.NumRows(), w.NumCols(), w.Stride()};
     made[m++] = &ok;
   }
@@ -1080,6 +1081,7 @@ void GruStreams::ResetLstmStreams(const std::vector<int32> &stream_reset_flag) {
 // the planes of the two matrices one pass of the per-timestep path multiplies with, in one multi-matrix conversion
 static bool GruStepPlanesOf(const CuMatrixBase &zr, const CuMatrixBase &mg, PlaneSet *pzr, PlaneSet *pmg, aslp_gru_step_h *out) {
   PlaneSet::ConvertSpec sp[2] = {Spec(pzr, zr), Spec(pmg, mg)};
+  if ((zr.NumCols() | mg.NumCols()) & 3) return false;   // (as LstmDir::RefreshStepPlanes: the step kernels take no ragged widths)
   if (!PlaneSet::ConvertMany(sp, 2)) return false;
   const S16View a = pzr->View(), b = pmg->View();
   out->zr_hi = a.hi; out->zr_lo = a.lo; out->zr_slot = a.slot; out->ldp_zr = a.ld;

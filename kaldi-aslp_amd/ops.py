@@ -67,6 +67,24 @@ def operand_planes(n):
         lib.aslp_gemm_operand_planes(before)
 
 
+def set_split16_ragged(on):
+    """split-fp16 layer products at sizes that are no multiple of 4 (aslp_gemm_split16_ragged): 1 = served (M, N >= 128 and K >= 64 remain),
+    0 = refused as shipped (default), -1 = what ASLP_GEMM_S16_RAGGED said"""
+    lib.aslp_gemm_split16_ragged(int(on))
+
+
+@contextlib.contextmanager
+def split16_ragged(on):
+    """products and conversions inside the block run with the switch at `on`; the setting in force before comes back on exit (pinned as an
+    explicit setting, as operand_planes does; set_split16_ragged(-1) hands the choice back to the environment)"""
+    before = lib.aslp_gemm_split16_ragged_get()
+    lib.aslp_gemm_split16_ragged(int(on))
+    try:
+        yield
+    finally:
+        lib.aslp_gemm_split16_ragged(before)
+
+
 def set_lstm_operand_pieces(n):
     """fp16 pieces per operand inside the persistent LSTM recurrences (aslp_lstm_operand_pieces): 2 = hi and lo' (fp32-equivalent operands),
     1 = hi alone (fp16 operands, fp32 accumulation), -1 = what ASLP_LSTM_PIECES said"""
