@@ -4,7 +4,13 @@
 // gemv launches per BatchNormalization step and ~15 + 5 blocking reductions per Xent::Eval;
 // here BN forward is ONE column-statistics pass + 1 write pass (optionally producing the following Sigmoid's
 // output as well), BN backward 1 statistics pass + 1 write pass (optionally absorbing that Sigmoid's backward), and Xent one pass with the row held in registers.
+//
+// The BatchNormalization kernels (three-launch, panel, cooperative, from-column-statistics) are built from one set of parts, each formula
+// written once: bn_fwd_accum / bn_fwd_sums, bn_fwd_finalize, bn_fwd_out4 + bn_fwd_act4 / bn_fwd_write (forward); bn_bwd_load_rows, bn_bwd_fold,
+// bn_bwd_accum / bn_bwd_sums, bn_bwd_col_update, bn_bwd_dvar_dmean, bn_bwd_coeffs, bn_bwd_write (backward); BnSlots (which rows and columns
+// a thread holds) and wg_max.  The host picks the path in bn_path_for (which aslp_bn_path reports) and the instantiation in with_slots.
 #include <atomic>
+#include <type_traits>
 
 #include "aslp_kernels.h"
 #include "colreduce.h"
@@ -32,6 +38,15 @@ __device__ __forceinline__ float4 load4_rows(const float *base, long ld, int r, 
 //   var = E[x^2] - mean^2  evaluated in double (53-bit sums of 24-bit data: no cancellation problem),
 // where the reference makes a second fp32 pass sum (x - mean)^2 (:193-204); the two agree to fp32
 // rounding of the reference's own result, far inside the 1e-4 parity tolerance.
+template <int VW>
+__device__ __forceinline__ void bn_fwd_accum(const float (&v)[VW], double (&acc)[3][VW]) {
+#pragma unroll
+  for (int i = 0; i < VW; i++) {
+    acc[0][i] += (double)v[i];
+    acc[1][i] += (double)(v[i] * v[i]);
+    acc[2][i] += (double)v[i] * (double)v[i];
+  }
+}
 struct BnSum1F {
   static constexpr bool kVec = true;
   const float *in; int ld;
@@ -39,12 +54,7 @@ struct BnSum1F {
   __device__ void operator()(int r, int c, double (&acc)[3][VW]) const {
     float x[VW];
     loadv<VW>(in + (long)r * ld + c, x);
-#pragma unroll
-    for (int i = 0; i < VW; i++) {
-      acc[0][i] += (double)x[i];
-      acc[1][i] += (double)(x[i] * x[i]);
-      acc[2][i] += (double)x[i] * (double)x[i];
-    }
+    bn_fwd_accum<VW>(x, acc);
   }
 };
 // The batch variance from the double sums, with `rows` itself as the divisor.  The fp32 1 / rows that scales the mean (as the reference's
@@ -55,20 +65,53 @@ __device__ __forceinline__ double bn_batch_var(double s0, double s2, int rows) {
   const double var = s2 / (double)rows - m * m;
   return var > 0.0 ? var : 0.0;
 }
+// One column's batch mean and inv_std from its three sums; `publish`: this thread also stores them and adds to the running sums (one
+// workgroup per column does).
+struct BnStat { float mu, is; };
+__device__ __forceinline__ BnStat bn_fwd_finalize(double s0, double s1, double s2, int rows, float inv_rows, float floor_, bool publish, int col,
+                                                  float *mean, float *inv_std, double *acc_means, double *acc_vars) {
+  // the reference's mean is an fp32 gemv result scaled by 1/B; a double sum rounded once to
+  // fp32 differs from it by < 1 ulp-of-sum.
+  const float mu = (float)s0 * inv_rows;
+  const double var = bn_batch_var(s0, s2, rows);
+  const float is = 1.0f / sqrtf((float)var + floor_);
+  if (publish) {
+    mean[col] = mu;
+    inv_std[col] = is;
+    if (acc_means) acc_means[col] += s0;
+    if (acc_vars) acc_vars[col] += s1;
+  }
+  return BnStat{mu, is};
+}
 struct BnSum1G {
   float inv_rows, floor_; int rows; float *mean, *inv_std; double *acc_means, *acc_vars;
   __device__ void operator()(int c, const double (&s)[3]) const {
-    // the reference's mean is an fp32 gemv result scaled by 1/B; a double sum rounded once to
-    // fp32 differs from it by < 1 ulp-of-sum.
-    mean[c] = (float)s[0] * inv_rows;
-    const double var = bn_batch_var(s[0], s[2], rows);
-    inv_std[c] = 1.0f / sqrtf((float)var + floor_);
-    if (acc_means) acc_means[c] += s[0];
-    if (acc_vars) acc_vars[c] += s[1];
+    bn_fwd_finalize(s[0], s[1], s[2], rows, inv_rows, floor_, true, c, mean, inv_std, acc_means, acc_vars);
   }
 };
 // write pass: xhat = (x - mean) * inv_std ; out = xhat * gamma + beta ; optionally act = sigmoid(out) for a Sigmoid
-// component fused behind the normalisation (then `out` itself may be NULL: nobody else reads it)
+// component fused behind the normalisation (then `out` itself may be NULL: nobody else reads it).  Four columns of row r at column c:
+// bn_fwd_out4 returns `out`, bn_fwd_act4 the Sigmoid's output it stores, bn_fwd_write4 is the two.
+__device__ __forceinline__ float4 bn_fwd_out4(const float4 &x, const float4 &m, const float4 &is, const float4 &g, const float4 &b, int r, int c,
+                                              float *out, int ldo, float *xhat, int ldx) {
+  float4 h, o;
+  h.x = (x.x - m.x) * is.x; h.y = (x.y - m.y) * is.y; h.z = (x.z - m.z) * is.z; h.w = (x.w - m.w) * is.w;
+  o.x = h.x * g.x + b.x; o.y = h.y * g.y + b.y; o.z = h.z * g.z + b.z; o.w = h.w * g.w + b.w;
+  if (xhat) *reinterpret_cast<float4 *>(xhat + (long)r * ldx + c) = h;
+  if (out) *reinterpret_cast<float4 *>(out + (long)r * ldo + c) = o;
+  return o;
+}
+__device__ __forceinline__ float4 bn_fwd_act4(const float4 &o, int r, int c, float *act, int lda) {
+  float4 y;
+  y.x = sigmoid_ref(o.x); y.y = sigmoid_ref(o.y); y.z = sigmoid_ref(o.z); y.w = sigmoid_ref(o.w);
+  *reinterpret_cast<float4 *>(act + (long)r * lda + c) = y;
+  return y;
+}
+__device__ __forceinline__ void bn_fwd_write4(const float4 &x, const float4 &m, const float4 &is, const float4 &g, const float4 &b, int r, int c,
+                                              float *out, int ldo, float *xhat, int ldx, float *act, int lda) {
+  const float4 o = bn_fwd_out4(x, m, is, g, b, r, c, out, ldo, xhat, ldx);
+  if (act) bn_fwd_act4(o, r, c, act, lda);
+}
 template <bool VEC>
 __global__ void __launch_bounds__(kBlock) bn_normalize_kernel(const float *in, int ldi, float *out, int ldo, float *xhat, int ldx,
                                                               const float *mean, const float *inv_std, const float *scale,
@@ -82,16 +125,7 @@ __global__ void __launch_bounds__(kBlock) bn_normalize_kernel(const float *in, i
       float4 x = *reinterpret_cast<const float4 *>(in + (long)r * ldi + c);
       float4 m = *reinterpret_cast<const float4 *>(mean + c), s = *reinterpret_cast<const float4 *>(inv_std + c);
       float4 g = *reinterpret_cast<const float4 *>(scale + c), b = *reinterpret_cast<const float4 *>(shift + c);
-      float4 h, o;
-      h.x = (x.x - m.x) * s.x; h.y = (x.y - m.y) * s.y; h.z = (x.z - m.z) * s.z; h.w = (x.w - m.w) * s.w;
-      o.x = h.x * g.x + b.x; o.y = h.y * g.y + b.y; o.z = h.z * g.z + b.z; o.w = h.w * g.w + b.w;
-      if (xhat) *reinterpret_cast<float4 *>(xhat + (long)r * ldx + c) = h;
-      if (out) *reinterpret_cast<float4 *>(out + (long)r * ldo + c) = o;
-      if (act) {
-        float4 y;
-        y.x = sigmoid_ref(o.x); y.y = sigmoid_ref(o.y); y.z = sigmoid_ref(o.z); y.w = sigmoid_ref(o.w);
-        *reinterpret_cast<float4 *>(act + (long)r * lda + c) = y;
-      }
+      bn_fwd_write4(x, m, s, g, b, r, c, out, ldo, xhat, ldx, act, lda);
     } else {
       float h = (in[(long)r * ldi + c] - mean[c]) * inv_std[c];
       if (xhat) xhat[(long)r * ldx + c] = h;
@@ -105,6 +139,14 @@ __global__ void __launch_bounds__(kBlock) bn_normalize_kernel(const float *in, i
 // backward statistics: S1 = sum dy, S2 = sum xhat*dy
 // `y` != NULL: a Sigmoid is fused behind the normalisation and `dy` is the diff w.r.t. ITS output;
 // the diff w.r.t. the BN output is dy * y * (1 - y), formed on the fly (nnet-activation.h:170-173)
+template <int VW>
+__device__ __forceinline__ void bn_bwd_accum(const float (&d)[VW], const float (&h)[VW], float (&acc)[2][VW]) {
+#pragma unroll
+  for (int i = 0; i < VW; i++) {
+    acc[0][i] += d[i];
+    acc[1][i] += h[i] * d[i];
+  }
+}
 struct BnBwdF {
   static constexpr bool kVec = true;
   const float *dy; int ldd; const float *xhat; int ldx; const float *y; int ldy;
@@ -119,32 +161,38 @@ struct BnBwdF {
 #pragma unroll
       for (int i = 0; i < VW; i++) d[i] = d[i] * yy[i] * (1.0f - yy[i]);
     }
-#pragma unroll
-    for (int i = 0; i < VW; i++) {
-      acc[0][i] += d[i];
-      acc[1][i] += h[i] * d[i];
-    }
+    bn_bwd_accum<VW>(d, h, acc);
   }
 };
+// One column's gradients from its sums S1, S2 and the values the column had before (g: the scale the forward pass used).
 // `step`: the component's SGD step (nnet-batch-normalization.h:280-284) is taken right here instead of in a launch of
-// its own; the write pass that follows still needs the scale the forward pass used, so it is kept in `scale_used`.
+// its own; the write pass that follows still needs the scale the forward pass used, so the callers keep it.
+__device__ __forceinline__ void bn_bwd_col_update(float s1, float s2, float mmt, float dshift_old, float dscale_old, float g, float shift_old, float neg_lr,
+                                                  bool step, int col, float *dscale, float *dshift, float *scale, float *shift) {
+  const float dsh = s1 + mmt * dshift_old, dsc = s2 + mmt * dscale_old;
+  dshift[col] = dsh;
+  dscale[col] = dsc;
+  if (step) {
+    scale[col] = g + neg_lr * dsc;
+    shift[col] = shift_old + neg_lr * dsh;
+  }
+}
 struct BnBwdG {
   float mmt; float *dscale, *dshift; float *s1, *s2;
   float *scale, *shift, *scale_used; float neg_lr; bool step;
   __device__ void operator()(int c, const float (&s)[2]) const {
-    const float dsh = s[0] + mmt * dshift[c], dsc = s[1] + mmt * dscale[c];
-    dshift[c] = dsh;
-    dscale[c] = dsc;
+    const float g = scale[c];
+    bn_bwd_col_update(s[0], s[1], mmt, dshift[c], dscale[c], g, step ? shift[c] : 0.f, neg_lr, step, c, dscale, dshift, scale, shift);
     s1[c] = s[0];
     s2[c] = s[1];
-    const float g = scale[c];
     scale_used[c] = g;
-    if (step) {
-      scale[c] = g + neg_lr * dsc;
-      shift[c] += neg_lr * dsh;
-    }
   }
 };
+// the two per-column derivatives of the in_diff below
+__device__ __forceinline__ void bn_bwd_dvar_dmean(float inv, float g, float s1, float s2, float &dvar, float &dmean) {
+  dvar = -0.5f * inv * inv * g * s2;         // = sum (x-mean) D * (-0.5 inv^3)
+  dmean = -inv * g * s1;
+}
 // in_diff: with D = dy*gamma, the reference's 4 steps (:238-276) reduce to
 //   dvar  = -0.5 * inv^3 * sum (x-mean) * D      = -0.5 * inv^2 * gamma * S2
 //   dmean = -inv * gamma * S1  ( - (2/B) dvar * sum(x-mean), which is 0 up to rounding )
@@ -182,8 +230,8 @@ __global__ void __launch_bounds__(kBlock) bn_backward_kernel(const float *dy, in
     for (int k = 0; k < W; k++) {
       float g = gv[k], inv = iv[k];
       float D = dyv[k] * g;
-      float dvar = -0.5f * inv * inv * g * s2v[k];         // = sum (x-mean) D * (-0.5 inv^3)
-      float dmean = -inv * g * s1v[k];
+      float dvar, dmean;
+      bn_bwd_dvar_dmean(inv, g, s1v[k], s2v[k], dvar, dmean);
       float xm = hv[k] / inv;
       Dv[k] = D;  // XsharpO_ <- dy*gamma, like the reference (:241-242)
       ov[k] = D * inv + xm * (2.0f * invB) * dvar + invB * dmean;
@@ -234,6 +282,144 @@ __device__ __forceinline__ T panel_total(const T *red, int a, int pc) {
   for (int w = 1; w < kPanelWaves; w++) s += red[(w * CG + cg) * (N * 4) + a * 4 + i];
   return s;
 }
+// The largest of one value per thread, in every thread of the workgroup.  red: kPanelWaves floats of LDS nobody else is using (a caller that
+// has just read them puts a barrier in front).
+__device__ __forceinline__ float wg_max(float v, float *red) {
+  v = wave_max(v);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  v = red[0];
+  for (int w = 1; w < kPanelWaves; w++) v = fmaxf(v, red[w]);
+  return v;
+}
+
+// ---- the parts the panel-resident kernels are built from ---------------------------------------------------------------------------
+// Which rows and columns a thread holds: workgroup q of the Q that share column panel p takes rows r0 .. r1 - 1 (a chunk of ceil(rows / Q)),
+// a thread of it row(k) for slot k at the four columns from c.  The single-workgroup panels are Q = 1, q = 0, p = blockIdx.x.
+// The parts take it BY VALUE: taken by reference every kernel built from them came out 1-3 % longer (a row's address formed from scratch
+// per slot instead of base + c once; profiles/bn_parts_text.txt).
+template <int CG>
+struct BnSlots {
+  static constexpr int L = kPanelThreads / CG;
+  int r0, r1, cg, lane, c;
+  __device__ __forceinline__ BnSlots(int rows, int Q, int q, int p) {
+    const int rp = (rows + Q - 1) / Q;
+    r0 = q * rp;
+    r1 = min(rows, r0 + rp);
+    cg = threadIdx.x % CG;
+    lane = threadIdx.x / CG;
+    c = (p * CG + cg) * 4;
+  }
+  __device__ __forceinline__ int row(int k) const { return r0 + lane + k * L; }
+};
+template <int SLOTS, int CG>
+__device__ __forceinline__ void bn_load_slots(BnSlots<CG> s, const float *base, int ld, float4 (&x)[SLOTS]) {
+#pragma unroll
+  for (int k = 0; k < SLOTS; k++) x[k] = load4_rows(base, ld, s.row(k), s.r1, s.c);
+}
+template <int SLOTS>
+__device__ __forceinline__ void bn_fwd_sums(const float4 (&x)[SLOTS], double (&acc)[3][4]) {
+#pragma unroll
+  for (int k = 0; k < SLOTS; k++) {
+    const float v[4] = {x[k].x, x[k].y, x[k].z, x[k].w};
+    bn_fwd_accum<4>(v, acc);
+  }
+}
+template <int SLOTS, int CG>
+__device__ __forceinline__ void bn_fwd_write(BnSlots<CG> s, const float4 (&x)[SLOTS], const float4 &m, const float4 &is, const float4 &g,
+                                             const float4 &b, float *out, int ldo, float *xhat, int ldx, float *act, int lda) {
+#pragma unroll
+  for (int k = 0; k < SLOTS; k++) {
+    const int r = s.row(k);
+    if (r >= s.r1) break;
+    bn_fwd_write4(x[k], m, is, g, b, r, s.c, out, ldo, xhat, ldx, act, lda);
+  }
+}
+// dy into d[], and into h[] x_hat as the forward pass stored it or (RECOMPUTE) the layer input it is formed from again in bn_bwd_fold
+template <int SLOTS, bool RECOMPUTE, int CG>
+__device__ __forceinline__ void bn_bwd_load_rows(BnSlots<CG> s, const float *dy, int ldd, const float *xhat, int ldx, const float *xin, int ldxin,
+                                                 float4 (&d)[SLOTS], float4 (&h)[SLOTS]) {
+#pragma unroll
+  for (int k = 0; k < SLOTS; k++) {
+    const int r = s.row(k);
+    d[k] = load4_rows(dy, ldd, r, s.r1, s.c);
+    if (RECOMPUTE) h[k] = load4_rows(xin, ldxin, r, s.r1, s.c);
+    else h[k] = load4_rows(xhat, ldx, r, s.r1, s.c);
+  }
+}
+// RECOMPUTE: h[] <- (x - mean) * inv_std with the forward kernel's own two operations (same bits; m, is: the panel's batch mean and inv_std).
+// HAS_Y: d[] <- the diff w.r.t. the BN output, dy * y * (1 - y), for a Sigmoid fused behind the normalisation.
+template <int SLOTS, bool HAS_Y, bool RECOMPUTE, int CG>
+__device__ __forceinline__ void bn_bwd_fold(BnSlots<CG> s, const float4 &m, const float4 &is, const float *y, int ldy, float4 (&d)[SLOTS],
+                                            float4 (&h)[SLOTS]) {
+  if (RECOMPUTE) {
+#pragma unroll
+    for (int k = 0; k < SLOTS; k++) {
+      if (s.row(k) < s.r1) { h[k].x = (h[k].x - m.x) * is.x; h[k].y = (h[k].y - m.y) * is.y; h[k].z = (h[k].z - m.z) * is.z; h[k].w = (h[k].w - m.w) * is.w; }
+    }
+  }
+  if (HAS_Y) {
+#pragma unroll
+    for (int k = 0; k < SLOTS; k++) {
+      const float4 yy = load4_rows(y, ldy, s.row(k), s.r1, s.c);
+      {
+        // products rounded on their own, never contracted into the sums below: the values a separate Sigmoid backward would
+        // have stored, so the folded and the unfolded executor agree bit for bit (HIP's __fmul_rn is a plain multiply)
+#pragma clang fp contract(off)
+        d[k].x = d[k].x * yy.x * (1.0f - yy.x); d[k].y = d[k].y * yy.y * (1.0f - yy.y);
+        d[k].z = d[k].z * yy.z * (1.0f - yy.z); d[k].w = d[k].w * yy.w * (1.0f - yy.w);
+      }
+    }
+  }
+}
+template <int SLOTS>
+__device__ __forceinline__ void bn_bwd_sums(const float4 (&d)[SLOTS], const float4 (&h)[SLOTS], float (&acc)[2][4]) {
+#pragma unroll
+  for (int k = 0; k < SLOTS; k++) {
+    const float dv[4] = {d[k].x, d[k].y, d[k].z, d[k].w}, hv[4] = {h[k].x, h[k].y, h[k].z, h[k].w};
+    bn_bwd_accum<4>(dv, hv, acc);
+  }
+}
+// per column of a thread's four: in_diff = D*inv + xm * ca + cb (stat: S1, S2 and the scale the forward pass used, per panel column)
+template <int CG>
+__device__ __forceinline__ void bn_bwd_coeffs(const float (&stat)[3][4 * CG], int cg, const float (&iv)[4], float invB, float (&gv)[4], float (&ca)[4],
+                                              float (&cb)[4]) {
+#pragma unroll
+  for (int i = 0; i < 4; i++) {
+    const float g = stat[2][cg * 4 + i];
+    float dvar, dmean;
+    bn_bwd_dvar_dmean(iv[i], g, stat[0][cg * 4 + i], stat[1][cg * 4 + i], dvar, dmean);
+    gv[i] = g;
+    ca[i] = (2.0f * invB) * dvar;
+    cb[i] = invB * dmean;
+  }
+}
+// The write pass of the backward kernels: in_diff, and D = dy * scale into xhat where the forward pass stored one (like the reference,
+// :241-242).  d[k] <- the in_diff written (for the planes), returns the largest |in_diff| of this thread.
+template <int SLOTS, bool RECOMPUTE, int CG>
+__device__ __forceinline__ float bn_bwd_write(BnSlots<CG> s, float4 (&d)[SLOTS], const float4 (&h)[SLOTS], const float (&gv)[4], const float (&iv)[4],
+                                              const float (&ca)[4], const float (&cb)[4], float *xhat, int ldx, float *in_diff, int ldi) {
+  float omax = 0.f;
+#pragma unroll
+  for (int k = 0; k < SLOTS; k++) {
+    const int r = s.row(k);
+    if (r >= s.r1) break;
+    const float dv[4] = {d[k].x, d[k].y, d[k].z, d[k].w}, hv[4] = {h[k].x, h[k].y, h[k].z, h[k].w};
+    float Dv[4], ov[4];
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+      const float D = dv[i] * gv[i];
+      const float xm = hv[i] / iv[i];
+      Dv[i] = D;
+      ov[i] = D * iv[i] + xm * ca[i] + cb[i];
+    }
+    if (!RECOMPUTE) *reinterpret_cast<float4 *>(xhat + (long)r * ldx + s.c) = make_float4(Dv[0], Dv[1], Dv[2], Dv[3]);
+    *reinterpret_cast<float4 *>(in_diff + (long)r * ldi + s.c) = make_float4(ov[0], ov[1], ov[2], ov[3]);
+    omax = s16_absmax4(omax, make_float4(ov[0], ov[1], ov[2], ov[3]));
+    d[k] = make_float4(ov[0], ov[1], ov[2], ov[3]);
+  }
+  return omax;
+}
 
 template <int CG, int SLOTS>
 __global__ void __launch_bounds__(kPanelThreads) bn_forward_panel(const float *__restrict__ in, int ldi, float *__restrict__ out, int ldo,
@@ -242,60 +428,25 @@ __global__ void __launch_bounds__(kPanelThreads) bn_forward_panel(const float *_
                                                            float *__restrict__ inv_std, double *__restrict__ acc_means,
                                                            double *__restrict__ acc_vars, float inv_rows, float floor_, int rows,
                                                            float *__restrict__ act, int lda) {
-  constexpr int L = kPanelThreads / CG;
   __shared__ double red[kPanelWaves * CG * 12];
   __shared__ float stat[2][4 * CG];
-  const int cg = threadIdx.x % CG, lane = threadIdx.x / CG;
-  const int c = ((int)blockIdx.x * CG + cg) * 4;
+  const BnSlots<CG> s(rows, 1, 0, (int)blockIdx.x);
   float4 x[SLOTS];
-#pragma unroll
-  for (int k = 0; k < SLOTS; k++) {
-    const int r = lane + k * L;
-    x[k] = load4_rows(in, ldi, r, rows, c);
-  }
-  const float4 g = *reinterpret_cast<const float4 *>(scale + c), b = *reinterpret_cast<const float4 *>(shift + c);   // (in the rows' round trip)
+  bn_load_slots<SLOTS>(s, in, ldi, x);
+  const float4 g = *reinterpret_cast<const float4 *>(scale + s.c), b = *reinterpret_cast<const float4 *>(shift + s.c);   // (in the rows' round trip)
   double acc[3][4] = {};
-#pragma unroll
-  for (int k = 0; k < SLOTS; k++) {
-    const float v[4] = {x[k].x, x[k].y, x[k].z, x[k].w};
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-      acc[0][i] += (double)v[i];
-      acc[1][i] += (double)(v[i] * v[i]);
-      acc[2][i] += (double)v[i] * (double)v[i];
-    }
-  }
+  bn_fwd_sums<SLOTS>(x, acc);
   panel_reduce<double, 3, CG>(acc, red);
-  if (threadIdx.x < 4 * CG) {  // the finalize of BnSum1G for one column
+  if (threadIdx.x < 4 * CG) {
     const int pc = threadIdx.x, col = (int)blockIdx.x * CG * 4 + pc;
     const double s0 = panel_total<double, 3, CG>(red, 0, pc), s1 = panel_total<double, 3, CG>(red, 1, pc), s2 = panel_total<double, 3, CG>(red, 2, pc);
-    const float mu = (float)s0 * inv_rows;
-    const double var = bn_batch_var(s0, s2, rows);
-    const float is = 1.0f / sqrtf((float)var + floor_);
-    mean[col] = mu;
-    inv_std[col] = is;
-    if (acc_means) acc_means[col] += s0;
-    if (acc_vars) acc_vars[col] += s1;
-    stat[0][pc] = mu;
-    stat[1][pc] = is;
+    const BnStat st = bn_fwd_finalize(s0, s1, s2, rows, inv_rows, floor_, true, col, mean, inv_std, acc_means, acc_vars);
+    stat[0][pc] = st.mu;
+    stat[1][pc] = st.is;
   }
   __syncthreads();
-  const float4 m = *reinterpret_cast<const float4 *>(&stat[0][cg * 4]), is = *reinterpret_cast<const float4 *>(&stat[1][cg * 4]);
-#pragma unroll
-  for (int k = 0; k < SLOTS; k++) {
-    const int r = lane + k * L;
-    if (r >= rows) break;
-    float4 h, o;
-    h.x = (x[k].x - m.x) * is.x; h.y = (x[k].y - m.y) * is.y; h.z = (x[k].z - m.z) * is.z; h.w = (x[k].w - m.w) * is.w;
-    o.x = h.x * g.x + b.x; o.y = h.y * g.y + b.y; o.z = h.z * g.z + b.z; o.w = h.w * g.w + b.w;
-    if (xhat) *reinterpret_cast<float4 *>(xhat + (long)r * ldx + c) = h;
-    if (out) *reinterpret_cast<float4 *>(out + (long)r * ldo + c) = o;
-    if (act) {
-      float4 y;
-      y.x = sigmoid_ref(o.x); y.y = sigmoid_ref(o.y); y.z = sigmoid_ref(o.z); y.w = sigmoid_ref(o.w);
-      *reinterpret_cast<float4 *>(act + (long)r * lda + c) = y;
-    }
-  }
+  const float4 m = *reinterpret_cast<const float4 *>(&stat[0][s.cg * 4]), is = *reinterpret_cast<const float4 *>(&stat[1][s.cg * 4]);
+  bn_fwd_write<SLOTS>(s, x, m, is, g, b, out, ldo, xhat, ldx, act, lda);
 }
 
 // RECOMPUTE: no normalised copy of the input was kept by the forward pass; x_hat = (x - mean) * inv_std is formed again from
@@ -308,94 +459,33 @@ __global__ void __launch_bounds__(kPanelThreads) bn_backward_panel(const float *
                                                             float *__restrict__ dshift, float mmt, float neg_lr, bool step,
                                                             float *__restrict__ in_diff, int ldi, int rows, const float *__restrict__ y, int ldy,
                                                             const float *__restrict__ xin, int ldxin, const float *__restrict__ mean) {
-  constexpr int L = kPanelThreads / CG;
   __shared__ float red[kPanelWaves * CG * 8];
   __shared__ float stat[3][4 * CG];  // S1, S2, the scale the forward pass used
-  const int cg = threadIdx.x % CG, lane = threadIdx.x / CG;
-  const int c = ((int)blockIdx.x * CG + cg) * 4;
+  const BnSlots<CG> s(rows, 1, 0, (int)blockIdx.x);
   float4 d[SLOTS], h[SLOTS];
-#pragma unroll
-  for (int k = 0; k < SLOTS; k++) {
-    const int r = lane + k * L;
-    d[k] = load4_rows(dy, ldd, r, rows, c);
-    if (RECOMPUTE) h[k] = load4_rows(xin, ldxin, r, rows, c);
-    else h[k] = load4_rows(xhat, ldx, r, rows, c);
-  }
-  if (RECOMPUTE) {
-    const float4 m = *reinterpret_cast<const float4 *>(mean + c), is = *reinterpret_cast<const float4 *>(inv_std + c);
-#pragma unroll
-    for (int k = 0; k < SLOTS; k++) {
-      const int r = lane + k * L;
-      if (r < rows) { h[k].x = (h[k].x - m.x) * is.x; h[k].y = (h[k].y - m.y) * is.y; h[k].z = (h[k].z - m.z) * is.z; h[k].w = (h[k].w - m.w) * is.w; }
-    }
-  }
-  if (HAS_Y) {
-#pragma unroll
-    for (int k = 0; k < SLOTS; k++) {
-      const int r = lane + k * L;
-      const float4 yy = load4_rows(y, ldy, r, rows, c);
-      {
-        // products rounded on their own, never contracted into the sums below: the values a separate Sigmoid backward would
-        // have stored, so the folded and the unfolded executor agree bit for bit (HIP's __fmul_rn is a plain multiply)
-#pragma clang fp contract(off)
-        d[k].x = d[k].x * yy.x * (1.0f - yy.x); d[k].y = d[k].y * yy.y * (1.0f - yy.y);
-        d[k].z = d[k].z * yy.z * (1.0f - yy.z); d[k].w = d[k].w * yy.w * (1.0f - yy.w);
-      }
-    }
-  }
+  bn_bwd_load_rows<SLOTS, RECOMPUTE>(s, dy, ldd, xhat, ldx, xin, ldxin, d, h);
+  const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
+  const float4 m = RECOMPUTE ? *reinterpret_cast<const float4 *>(mean + s.c) : zero4, is = RECOMPUTE ? *reinterpret_cast<const float4 *>(inv_std + s.c) : zero4;
+  bn_bwd_fold<SLOTS, HAS_Y, RECOMPUTE>(s, m, is, y, ldy, d, h);
   float acc[2][4] = {};
-#pragma unroll
-  for (int k = 0; k < SLOTS; k++) {
-    acc[0][0] += d[k].x; acc[0][1] += d[k].y; acc[0][2] += d[k].z; acc[0][3] += d[k].w;
-    acc[1][0] += h[k].x * d[k].x; acc[1][1] += h[k].y * d[k].y; acc[1][2] += h[k].z * d[k].z; acc[1][3] += h[k].w * d[k].w;
-  }
+  bn_bwd_sums<SLOTS>(d, h, acc);
   panel_reduce<float, 2, CG>(acc, red);
-  if (threadIdx.x < 4 * CG) {  // BnBwdG for one column
+  if (threadIdx.x < 4 * CG) {
     const int pc = threadIdx.x, col = (int)blockIdx.x * CG * 4 + pc;
     const float s1 = panel_total<float, 2, CG>(red, 0, pc), s2 = panel_total<float, 2, CG>(red, 1, pc);
-    const float dsh = s1 + mmt * dshift[col], dsc = s2 + mmt * dscale[col];
-    dshift[col] = dsh;
-    dscale[col] = dsc;
     const float g = scale[col];
-    if (step) {
-      scale[col] = g + neg_lr * dsc;
-      shift[col] += neg_lr * dsh;
-    }
+    bn_bwd_col_update(s1, s2, mmt, dshift[col], dscale[col], g, step ? shift[col] : 0.f, neg_lr, step, col, dscale, dshift, scale, shift);
     stat[0][pc] = s1;
     stat[1][pc] = s2;
     stat[2][pc] = g;
   }
   __syncthreads();
   if (in_diff == nullptr) return;
-  const float invB = 1.0f / (float)rows;
-  const float4 iv4 = *reinterpret_cast<const float4 *>(inv_std + c);
+  const float4 iv4 = *reinterpret_cast<const float4 *>(inv_std + s.c);
   const float iv[4] = {iv4.x, iv4.y, iv4.z, iv4.w};
-  float gv[4], ca[4], cb[4];  // per column: in_diff = D*inv + xm * ca + cb
-#pragma unroll
-  for (int i = 0; i < 4; i++) {
-    const float g = stat[2][cg * 4 + i], inv = iv[i];
-    const float dvar = -0.5f * inv * inv * g * stat[1][cg * 4 + i];
-    const float dmean = -inv * g * stat[0][cg * 4 + i];
-    gv[i] = g;
-    ca[i] = (2.0f * invB) * dvar;
-    cb[i] = invB * dmean;
-  }
-#pragma unroll
-  for (int k = 0; k < SLOTS; k++) {
-    const int r = lane + k * L;
-    if (r >= rows) break;
-    const float dv[4] = {d[k].x, d[k].y, d[k].z, d[k].w}, hv[4] = {h[k].x, h[k].y, h[k].z, h[k].w};
-    float Dv[4], ov[4];
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-      const float D = dv[i] * gv[i];
-      const float xm = hv[i] / iv[i];
-      Dv[i] = D;
-      ov[i] = D * iv[i] + xm * ca[i] + cb[i];
-    }
-    if (!RECOMPUTE) *reinterpret_cast<float4 *>(xhat + (long)r * ldx + c) = make_float4(Dv[0], Dv[1], Dv[2], Dv[3]);
-    *reinterpret_cast<float4 *>(in_diff + (long)r * ldi + c) = make_float4(ov[0], ov[1], ov[2], ov[3]);
-  }
+  float gv[4], ca[4], cb[4];
+  bn_bwd_coeffs<CG>(stat, s.cg, iv, 1.0f / (float)rows, gv, ca, cb);
+  bn_bwd_write<SLOTS, RECOMPUTE>(s, d, h, gv, iv, ca, cb, xhat, ldx, in_diff, ldi);
 }
 
 // ---- cooperative panels ---------------------------------------------------------------------------------------------
@@ -448,31 +538,16 @@ __global__ void __launch_bounds__(kPanelThreads) bn_forward_coop(const float *__
                                                           float *__restrict__ inv_std, double *__restrict__ acc_means,
                                                           double *__restrict__ acc_vars, float inv_rows, float floor_, int rows,
                                                           float *__restrict__ act, int lda, int Q, unsigned long long *inbox, unsigned *err) {
-  constexpr int CG = kCoopCG, L = kCoopLanes;
+  constexpr int CG = kCoopCG;
   __shared__ double red[kPanelWaves * CG * 12];
   __shared__ float stat[2][4 * CG];
   const int P = gridDim.x / Q, p = blockIdx.x % P, q = blockIdx.x / P;
-  const int rp = (rows + Q - 1) / Q, r0 = q * rp, r1 = min(rows, r0 + rp);
-  const int cg = threadIdx.x % CG, lane = threadIdx.x / CG;
-  const int c = (p * CG + cg) * 4;
+  const BnSlots<CG> s(rows, Q, q, p);
   float4 x[SLOTS];
-#pragma unroll
-  for (int k = 0; k < SLOTS; k++) {
-    const int r = r0 + lane + k * L;
-    x[k] = load4_rows(in, ldi, r, r1, c);
-  }
-  const float4 g = *reinterpret_cast<const float4 *>(scale + c), b = *reinterpret_cast<const float4 *>(shift + c);   // (in the rows' round trip)
+  bn_load_slots<SLOTS>(s, in, ldi, x);
+  const float4 g = *reinterpret_cast<const float4 *>(scale + s.c), b = *reinterpret_cast<const float4 *>(shift + s.c);   // (in the rows' round trip)
   double acc[3][4] = {};
-#pragma unroll
-  for (int k = 0; k < SLOTS; k++) {
-    const float v[4] = {x[k].x, x[k].y, x[k].z, x[k].w};
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-      acc[0][i] += (double)v[i];
-      acc[1][i] += (double)(v[i] * v[i]);
-      acc[2][i] += (double)v[i] * (double)v[i];
-    }
-  }
+  bn_fwd_sums<SLOTS>(x, acc);
   panel_reduce<double, 3, CG>(acc, red);
   if (threadIdx.x < 4 * CG) {
     const int pc = threadIdx.x, col = p * CG * 4 + pc;
@@ -486,35 +561,13 @@ __global__ void __launch_bounds__(kPanelThreads) bn_forward_coop(const float *__
       s1 += __longlong_as_double((long long)got[qw][1]);
       s2 += __longlong_as_double((long long)got[qw][2]);
     }
-    const float mu = (float)s0 * inv_rows;
-    const double var = bn_batch_var(s0, s2, rows);
-    const float is = 1.0f / sqrtf((float)var + floor_);
-    if (q == 0) {
-      mean[col] = mu;
-      inv_std[col] = is;
-      if (acc_means) acc_means[col] += s0;
-      if (acc_vars) acc_vars[col] += s1;
-    }
-    stat[0][pc] = mu;
-    stat[1][pc] = is;
+    const BnStat st = bn_fwd_finalize(s0, s1, s2, rows, inv_rows, floor_, q == 0, col, mean, inv_std, acc_means, acc_vars);
+    stat[0][pc] = st.mu;
+    stat[1][pc] = st.is;
   }
   __syncthreads();
-  const float4 m = *reinterpret_cast<const float4 *>(&stat[0][cg * 4]), is = *reinterpret_cast<const float4 *>(&stat[1][cg * 4]);
-#pragma unroll
-  for (int k = 0; k < SLOTS; k++) {
-    const int r = r0 + lane + k * L;
-    if (r >= r1) break;
-    float4 h, o;
-    h.x = (x[k].x - m.x) * is.x; h.y = (x[k].y - m.y) * is.y; h.z = (x[k].z - m.z) * is.z; h.w = (x[k].w - m.w) * is.w;
-    o.x = h.x * g.x + b.x; o.y = h.y * g.y + b.y; o.z = h.z * g.z + b.z; o.w = h.w * g.w + b.w;
-    if (xhat) *reinterpret_cast<float4 *>(xhat + (long)r * ldx + c) = h;
-    if (out) *reinterpret_cast<float4 *>(out + (long)r * ldo + c) = o;
-    if (act) {
-      float4 y;
-      y.x = sigmoid_ref(o.x); y.y = sigmoid_ref(o.y); y.z = sigmoid_ref(o.z); y.w = sigmoid_ref(o.w);
-      *reinterpret_cast<float4 *>(act + (long)r * lda + c) = y;
-    }
-  }
+  const float4 m = *reinterpret_cast<const float4 *>(&stat[0][s.cg * 4]), is = *reinterpret_cast<const float4 *>(&stat[1][s.cg * 4]);
+  bn_fwd_write<SLOTS>(s, x, m, is, g, b, out, ldo, xhat, ldx, act, lda);
 }
 
 // BatchNormalization forward whose column statistics come from the producer of `in` (the forward GEMM's epilogue,
@@ -528,20 +581,15 @@ __global__ void __launch_bounds__(kPanelThreads) bn_forward_stats_kernel(const f
                                                                         double *__restrict__ acc_means, double *__restrict__ acc_vars, float inv_rows,
                                                                         float floor_, int rows, float *__restrict__ act, int lda, int Q,
                                                                         const double *__restrict__ part, int groups, int ldp, S16Out po) {
-  constexpr int CG = kCoopCG, L = kCoopLanes, COLS = kCoopCols, SL = kPanelThreads / COLS;  // SL partial-sum slices per column
+  constexpr int CG = kCoopCG, COLS = kCoopCols, SL = kPanelThreads / COLS;  // SL partial-sum slices per column
   __shared__ double red[3][SL][COLS];
   __shared__ float stat[2][COLS];
   const int P = gridDim.x / Q, p = blockIdx.x % P, q = blockIdx.x / P;
-  const int rp = (rows + Q - 1) / Q, r0 = q * rp, r1 = min(rows, r0 + rp);
-  const int cg = threadIdx.x % CG, lane = threadIdx.x / CG;
-  const int c = (p * CG + cg) * 4;
+  const BnSlots<CG> s(rows, Q, q, p);
+  const int c = s.c;
   // the rows first (<= kStatSlots per thread, the host sizes Q for that): their latency overlaps the statistics below
   float4 x[kStatSlots];
-#pragma unroll
-  for (int k = 0; k < kStatSlots; k++) {
-    const int r = r0 + lane + k * L;
-    x[k] = load4_rows(in, ldi, r, r1, c);
-  }
+  bn_load_slots<kStatSlots>(s, in, ldi, x);
   // everything else this workgroup reads goes out behind them in the same round: scale and shift, the planes' bound, and the statistics'
   // partial sums four groups at a time (a loop that adds one group per iteration is one round trip to L2 per iteration)
   const float4 g = *reinterpret_cast<const float4 *>(scale + c), b = *reinterpret_cast<const float4 *>(shift + c);
@@ -570,33 +618,20 @@ __global__ void __launch_bounds__(kPanelThreads) bn_forward_stats_kernel(const f
     double s0 = 0.0, s1 = 0.0, s2 = 0.0;
 #pragma unroll
     for (int sl = 0; sl < SL; sl++) { s0 += red[0][sl][pc]; s1 += red[1][sl][pc]; s2 += red[2][sl][pc]; }
-    const float mu = (float)s0 * inv_rows;   // as bn_forward_coop
-    const double var = bn_batch_var(s0, s2, rows);
-    const float is = 1.0f / sqrtf((float)var + floor_);
-    if (q == 0) {
-      mean[col] = mu;
-      inv_std[col] = is;
-      if (acc_means) acc_means[col] += s0;
-      if (acc_vars) acc_vars[col] += s1;
-    }
-    stat[0][pc] = mu;
-    stat[1][pc] = is;
+    const BnStat st = bn_fwd_finalize(s0, s1, s2, rows, inv_rows, floor_, q == 0, col, mean, inv_std, acc_means, acc_vars);   // as bn_forward_coop
+    stat[0][pc] = st.mu;
+    stat[1][pc] = st.is;
   }
   __syncthreads();
-  const float4 m = *reinterpret_cast<const float4 *>(&stat[0][cg * 4]), is = *reinterpret_cast<const float4 *>(&stat[1][cg * 4]);
+  const float4 m = *reinterpret_cast<const float4 *>(&stat[0][s.cg * 4]), is = *reinterpret_cast<const float4 *>(&stat[1][s.cg * 4]);
   const float pscale = po.hi ? ldexpf(1.f, s16_exponent(bound_bits)) : 0.f;
 #pragma unroll
   for (int k = 0; k < kStatSlots; k++) {
-    const int r = r0 + lane + k * L;
-    if (r >= r1) break;
-    float4 h, o;
-    h.x = (x[k].x - m.x) * is.x; h.y = (x[k].y - m.y) * is.y; h.z = (x[k].z - m.z) * is.z; h.w = (x[k].w - m.w) * is.w;
-    o.x = h.x * g.x + b.x; o.y = h.y * g.y + b.y; o.z = h.z * g.z + b.z; o.w = h.w * g.w + b.w;
-    if (out) *reinterpret_cast<float4 *>(out + (long)r * ldo + c) = o;
+    const int r = s.row(k);
+    if (r >= s.r1) break;
+    const float4 o = bn_fwd_out4(x[k], m, is, g, b, r, c, out, ldo, nullptr, 0);
     if (act) {
-      float4 y;
-      y.x = sigmoid_ref(o.x); y.y = sigmoid_ref(o.y); y.z = sigmoid_ref(o.z); y.w = sigmoid_ref(o.w);
-      *reinterpret_cast<float4 *>(act + (long)r * lda + c) = y;
+      const float4 y = bn_fwd_act4(o, r, c, act, lda);
       if (po.hi) {   // the planes of the activations for the products that read them (bound: a sigmoid's 1)
         half4 hi, lo;
         s16_split4(y, pscale, &hi, &lo);
@@ -609,10 +644,10 @@ __global__ void __launch_bounds__(kPanelThreads) bn_forward_stats_kernel(const f
 
 // The largest of one value per workgroup, in every workgroup of a launch whose workgroups are all resident at once (the host checks: they
 // wait for each other).  They meet in gmax, one 8-byte word each: this launch's token | the value's bits -- nothing to reset, an older
-// launch's word never matches.  wg_max: the workgroup's value (in every thread); red: >= kPanelWaves floats of LDS nobody else is using.
-__device__ __forceinline__ float coop_grid_max(float wg_max, unsigned long long *gmax, unsigned token, unsigned *err, float *red) {
+// launch's word never matches.  mine: the workgroup's value (in every thread); red: >= kPanelWaves floats of LDS nobody else is using.
+__device__ __forceinline__ float coop_grid_max(float mine, unsigned long long *gmax, unsigned token, unsigned *err, float *red) {
   if (threadIdx.x == 0)
-    __hip_atomic_store(gmax + blockIdx.x, ((unsigned long long)token << 32) | (unsigned long long)__float_as_uint(wg_max), __ATOMIC_RELAXED,
+    __hip_atomic_store(gmax + blockIdx.x, ((unsigned long long)token << 32) | (unsigned long long)__float_as_uint(mine), __ATOMIC_RELAXED,
                        __HIP_MEMORY_SCOPE_AGENT);
   float gm = 0.f;
   bool ok = true;
@@ -626,13 +661,8 @@ __device__ __forceinline__ float coop_grid_max(float wg_max, unsigned long long 
     }
   }
   if (!ok) __hip_atomic_fetch_add(err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  gm = wave_max(gm);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = gm;
-  __syncthreads();
-  gm = red[0];
-  for (int w = 1; w < kPanelWaves; w++) gm = fmaxf(gm, red[w]);
-  return gm;
+  __syncthreads();   // (a caller may have just read red[])
+  return wg_max(gm, red);
 }
 
 // Matrices (up to kS16MaxJobs, blockIdx.y) copied (optional) and their fp16 planes made in ONE launch (coop_convert_launch: the network
@@ -690,11 +720,7 @@ __global__ void __launch_bounds__(kPanelThreads) copy_planes_coop(CoopConvJobs j
     }
     if (job.parts == nullptr) m = s16_absmax4(m, v[k]);
   }
-  m = wave_max(m);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
-  __syncthreads();
-  m = red[0];
-  for (int w = 1; w < kPanelWaves; w++) m = fmaxf(m, red[w]);
+  m = wg_max(m, red);
   unsigned mbits = __float_as_uint(m);
   if (job.parts == nullptr) mbits = __float_as_uint(coop_grid_max(m, gmax + (size_t)blockIdx.y * gridDim.x, token, err, red));
   if (blockIdx.x == 0 && threadIdx.x == 0) *job.pl.slot = mbits;
@@ -719,21 +745,14 @@ __global__ void __launch_bounds__(kPanelThreads) bn_backward_coop(const float *_
                                                            const float *__restrict__ xin, int ldxin, const float *__restrict__ mean, int Q,
                                                            unsigned long long *inbox, unsigned *err, float *__restrict__ max_parts, S16Out po,
                                                            unsigned long long *gmax, unsigned token) {
-  constexpr int CG = kCoopCG, L = kCoopLanes;
+  constexpr int CG = kCoopCG;
   __shared__ float red[kPanelWaves * CG * 8];
   __shared__ float stat[3][4 * CG];  // S1, S2, the scale the forward pass used
   const int P = gridDim.x / Q, p = blockIdx.x % P, q = blockIdx.x / P;
-  const int rp = (rows + Q - 1) / Q, r0 = q * rp, r1 = min(rows, r0 + rp);
-  const int cg = threadIdx.x % CG, lane = threadIdx.x / CG;
-  const int c = (p * CG + cg) * 4;
+  const BnSlots<CG> s(rows, Q, q, p);
+  const int c = s.c;
   float4 d[SLOTS], h[SLOTS];
-#pragma unroll
-  for (int k = 0; k < SLOTS; k++) {
-    const int r = r0 + lane + k * L;
-    d[k] = load4_rows(dy, ldd, r, r1, c);
-    if (RECOMPUTE) h[k] = load4_rows(xin, ldxin, r, r1, c);
-    else h[k] = load4_rows(xhat, ldx, r, r1, c);
-  }
+  bn_bwd_load_rows<SLOTS, RECOMPUTE>(s, dy, ldd, xhat, ldx, xin, ldxin, d, h);
   // the per-column values go out in the rows' round trip (a load issued where its value is first used costs a trip to L2 of its own there).
   // The scale the forward pass used: workgroup q == 0 rewrites it (the folded SGD step) only after it has seen every partial of the panel,
   // and a workgroup publishes its partial only after this load has returned (the wait in front of the exchange).
@@ -743,32 +762,10 @@ __global__ void __launch_bounds__(kPanelThreads) bn_backward_coop(const float *_
   const float g_fwd = col_thread ? scale[my_col] : 0.f;
   const float dsh_old = col_thread && q == 0 ? dshift[my_col] : 0.f, dsc_old = col_thread && q == 0 ? dscale[my_col] : 0.f;
   const float sh_old = col_thread && q == 0 && step ? shift[my_col] : 0.f;
-  if (RECOMPUTE) {
-    const float4 m = *reinterpret_cast<const float4 *>(mean + c), is = iv4;
-#pragma unroll
-    for (int k = 0; k < SLOTS; k++) {
-      const int r = r0 + lane + k * L;
-      if (r < r1) { h[k].x = (h[k].x - m.x) * is.x; h[k].y = (h[k].y - m.y) * is.y; h[k].z = (h[k].z - m.z) * is.z; h[k].w = (h[k].w - m.w) * is.w; }
-    }
-  }
-  if (HAS_Y) {
-#pragma unroll
-    for (int k = 0; k < SLOTS; k++) {
-      const int r = r0 + lane + k * L;
-      const float4 yy = load4_rows(y, ldy, r, r1, c);
-      {
-#pragma clang fp contract(off)
-        d[k].x = d[k].x * yy.x * (1.0f - yy.x); d[k].y = d[k].y * yy.y * (1.0f - yy.y);
-        d[k].z = d[k].z * yy.z * (1.0f - yy.z); d[k].w = d[k].w * yy.w * (1.0f - yy.w);
-      }
-    }
-  }
+  const float4 m4 = RECOMPUTE ? *reinterpret_cast<const float4 *>(mean + c) : make_float4(0.f, 0.f, 0.f, 0.f);
+  bn_bwd_fold<SLOTS, HAS_Y, RECOMPUTE>(s, m4, iv4, y, ldy, d, h);
   float acc[2][4] = {};
-#pragma unroll
-  for (int k = 0; k < SLOTS; k++) {
-    acc[0][0] += d[k].x; acc[0][1] += d[k].y; acc[0][2] += d[k].z; acc[0][3] += d[k].w;
-    acc[1][0] += h[k].x * d[k].x; acc[1][1] += h[k].y * d[k].y; acc[1][2] += h[k].z * d[k].z; acc[1][3] += h[k].w * d[k].w;
-  }
+  bn_bwd_sums<SLOTS>(d, h, acc);
   panel_reduce<float, 2, CG>(acc, red);
   if (threadIdx.x < 4 * CG) {
     const int pc = threadIdx.x, col = p * CG * 4 + pc;
@@ -783,56 +780,17 @@ __global__ void __launch_bounds__(kPanelThreads) bn_backward_coop(const float *_
     stat[0][pc] = s1;
     stat[1][pc] = s2;
     stat[2][pc] = g;
-    if (q == 0) {
-      const float dsh = s1 + mmt * dsh_old, dsc = s2 + mmt * dsc_old;
-      dshift[col] = dsh;
-      dscale[col] = dsc;
-      if (step) {
-        scale[col] = g + neg_lr * dsc;
-        shift[col] = sh_old + neg_lr * dsh;
-      }
-    }
+    if (q == 0) bn_bwd_col_update(s1, s2, mmt, dsh_old, dsc_old, g, sh_old, neg_lr, step, col, dscale, dshift, scale, shift);
   }
   __syncthreads();
-  const float invB = 1.0f / (float)rows;
   if (in_diff != nullptr) {
     const float iv[4] = {iv4.x, iv4.y, iv4.z, iv4.w};
-    float gv[4], ca[4], cb[4];  // per column: in_diff = D*inv + xm * ca + cb
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-      const float g = stat[2][cg * 4 + i], inv = iv[i];
-      const float dvar = -0.5f * inv * inv * g * stat[1][cg * 4 + i];
-      const float dmean = -inv * g * stat[0][cg * 4 + i];
-      gv[i] = g;
-      ca[i] = (2.0f * invB) * dvar;
-      cb[i] = invB * dmean;
-    }
-    float omax = 0.f;
-#pragma unroll
-    for (int k = 0; k < SLOTS; k++) {
-      const int r = r0 + lane + k * L;
-      if (r >= r1) break;
-      const float dv[4] = {d[k].x, d[k].y, d[k].z, d[k].w}, hv[4] = {h[k].x, h[k].y, h[k].z, h[k].w};
-      float Dv[4], ov[4];
-#pragma unroll
-      for (int i = 0; i < 4; i++) {
-        const float D = dv[i] * gv[i];
-        const float xm = hv[i] / iv[i];
-        Dv[i] = D;
-        ov[i] = D * iv[i] + xm * ca[i] + cb[i];
-      }
-      if (!RECOMPUTE) *reinterpret_cast<float4 *>(xhat + (long)r * ldx + c) = make_float4(Dv[0], Dv[1], Dv[2], Dv[3]);
-      *reinterpret_cast<float4 *>(in_diff + (long)r * ldi + c) = make_float4(ov[0], ov[1], ov[2], ov[3]);
-      omax = s16_absmax4(omax, make_float4(ov[0], ov[1], ov[2], ov[3]));
-      d[k] = make_float4(ov[0], ov[1], ov[2], ov[3]);   // (kept for the planes below)
-    }
+    float gv[4], ca[4], cb[4];
+    bn_bwd_coeffs<CG>(stat, s.cg, iv, 1.0f / (float)rows, gv, ca, cb);
+    const float omax = bn_bwd_write<SLOTS, RECOMPUTE>(s, d, h, gv, iv, ca, cb, xhat, ldx, in_diff, ldi);   // (d[] <- in_diff, kept for the planes below)
     if (max_parts != nullptr || po.hi != nullptr) {   // this workgroup's largest |in_diff|
-      omax = wave_max(omax);
       __syncthreads();            // (red[] is free: every thread is past the statistics)
-      if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = omax;
-      __syncthreads();
-      float m = red[0];
-      for (int w = 1; w < kPanelWaves; w++) m = fmaxf(m, red[w]);
+      const float m = wg_max(omax, red);
       // ... for the conversion of in_diff, which takes its scale from these (split16.h) ...
       if (max_parts != nullptr && threadIdx.x == 0) max_parts[blockIdx.x] = m;
       // ... or the planes from this launch: the workgroups' maxima meet (coop_grid_max) and every workgroup scales its rows by the matrix
@@ -844,8 +802,8 @@ __global__ void __launch_bounds__(kPanelThreads) bn_backward_coop(const float *_
         const float ps = ldexpf(1.f, s16_exponent(mbits));
 #pragma unroll
         for (int k = 0; k < SLOTS; k++) {
-          const int r = r0 + lane + k * L;
-          if (r >= r1) break;
+          const int r = s.row(k);
+          if (r >= s.r1) break;
           half4 hi, lo;
           s16_split4(d[k], ps, &hi, &lo);
           *reinterpret_cast<half4 *>(po.hi + (long)r * po.ld + c) = hi;
@@ -909,20 +867,42 @@ inline CoopShape bn_coop_shape(int rows, int cols) {
   return none;
 }
 
-// 0: the three-launch path; else column groups per workgroup and row slots per thread (4, 8 or 16).  Measured on the cfg2 step
-// (1024 x 2048): 4 groups x 256 threads 729 k frames/s, 2 groups (32-byte row segments) 698 k, 1024-thread workgroups with 4 / 8
-// groups 680 k / 713 k, the three-launch path 717-721 k.
-struct PanelShape { int cg, slots; };
-inline PanelShape bn_panel_shape(int rows, int cols) {
+// 0: the three-launch path; else the row slots per thread (4, 8 or 16) of a panel of kPanelCG column groups per workgroup.  Measured on
+// the cfg2 step (1024 x 2048): 4 groups x 256 threads 729 k frames/s, 2 groups (32-byte row segments) 698 k, 1024-thread workgroups with
+// 4 / 8 groups 680 k / 713 k, the three-launch path 717-721 k.
+constexpr int kPanelCG = 4;
+inline int bn_panel_shape(int rows, int cols) {
   static const int forced = [] { const char *e = getenv("ASLP_BN_PANEL"); return e ? atoi(e) : -1; }();
-  PanelShape none = {0, 0};
-  if (forced == 0) return none;
-  const int cg = 4;
-  if (cols % (4 * cg) != 0) return none;
-  const int lanes = kPanelThreads / cg;
+  if (forced == 0 || cols % (4 * kPanelCG) != 0) return 0;
   for (int slots : {4, 8, 16})
-    if (rows <= slots * lanes) return PanelShape{cg, slots};
-  return none;
+    if (rows <= slots * (kPanelThreads / kPanelCG)) return slots;
+  return 0;
+}
+// The kernels that serve [rows x cols]: 0 the three launches, 1 the single-workgroup panels, 2 the cooperative panels (q workgroups per
+// panel); vec: every operand allows 16-byte accesses.  The launchers and aslp_bn_path both ask here.
+struct BnPath { int path, q, slots; };
+inline BnPath bn_path_for(int rows, int cols, bool vec) {
+  const int slots = vec ? bn_panel_shape(rows, cols) : 0;
+  if (!slots) return BnPath{0, 0, 0};
+  const CoopShape cs = bn_coop_shape(rows, cols);
+  if (cs.q && coop_state().inbox) return BnPath{2, cs.q, cs.slots};
+  return BnPath{1, 1, slots};
+}
+// 16-byte accesses to rows of `stride` floats from p on (a vector: stride 0)
+inline bool vec_ok(const void *p, int stride = 0) { return aligned16(p) && stride % 4 == 0; }
+// f(std::integral_constant) for the slot count / the flag given at run time: the kernels' template arguments
+template <typename F>
+void with_slots(int slots, F &&f) {
+  switch (slots) {
+    case 4: f(std::integral_constant<int, 4>{}); break;
+    case 8: f(std::integral_constant<int, 8>{}); break;
+    case 16: f(std::integral_constant<int, 16>{}); break;
+  }
+}
+template <typename F>
+void with_flag(bool flag, F &&f) {
+  if (flag) f(std::true_type{});
+  else f(std::false_type{});
 }
 
 // ---- Xent ------------------------------------------------------------------------------
@@ -1320,36 +1300,27 @@ void aslp_bn_forward_act(const float *in, MatrixDim d, float *out, int out_strid
   if (d.rows <= 0 || d.cols <= 0) return;
   if (!out && !act_out) { set_error("aslp_bn_forward: no output"); return; }
   const float invB = 1.0f / (float)d.rows;
-  const bool in_vec = aligned16(in) && d.stride % 4 == 0;
-  bool vec = d.cols % 4 == 0 && d.stride % 4 == 0 && (!out || (out_stride % 4 == 0 && aligned16(out))) &&
-             (!xhat || (xhat_stride % 4 == 0 && aligned16(xhat))) && (!act_out || (act_stride % 4 == 0 && aligned16(act_out))) &&
-             aligned16(in) && aligned16(mean) && aligned16(inv_std) && aligned16(scale) && aligned16(shift);
-  const PanelShape ps = vec ? bn_panel_shape(d.rows, d.cols) : PanelShape{0, 0};
-  const CoopShape cs = (vec && ps.cg) ? bn_coop_shape(d.rows, d.cols) : CoopShape{0, 0};
-  if (cs.q && coop_state().inbox) {
+  const bool in_vec = vec_ok(in, d.stride);
+  const bool vec = d.cols % 4 == 0 && in_vec && (!out || vec_ok(out, out_stride)) && (!xhat || vec_ok(xhat, xhat_stride)) &&
+                   (!act_out || vec_ok(act_out, act_stride)) && vec_ok(mean) && vec_ok(inv_std) && vec_ok(scale) && vec_ok(shift);
+  const BnPath bp = bn_path_for(d.rows, d.cols, vec);
+  const dim3 block(kPanelThreads);
+  if (bp.path == 2) {
     CoopState &st = coop_state();
-    const dim3 grid((d.cols / kCoopCols) * cs.q), block(kPanelThreads);
-#define ASLP_BN_FWD_COOP(SLOTS)                                                                                                             \
-    case SLOTS:                                                                                                                             \
-      hipLaunchKernelGGL((bn_forward_coop<SLOTS>), grid, block, 0, cur_stream(), in, d.stride, out, out_stride, xhat, xhat_stride, scale, shift, \
-                         mean, inv_std, acc_means, acc_vars, invB, var_floor, d.rows, act_out, act_stride, cs.q, st.inbox, st.err);           \
-      break;
-    switch (cs.slots) { ASLP_BN_FWD_COOP(4) ASLP_BN_FWD_COOP(8) ASLP_BN_FWD_COOP(16) }
-#undef ASLP_BN_FWD_COOP
+    const dim3 grid((d.cols / kCoopCols) * bp.q);
+    with_slots(bp.slots, [&](auto S) {
+      hipLaunchKernelGGL((bn_forward_coop<decltype(S)::value>), grid, block, 0, cur_stream(), in, d.stride, out, out_stride, xhat, xhat_stride, scale, shift,
+                         mean, inv_std, acc_means, acc_vars, invB, var_floor, d.rows, act_out, act_stride, bp.q, st.inbox, st.err);
+    });
     check_launch("bn_forward_coop");
     return;
   }
-  if (ps.cg) {
-    const dim3 grid(d.cols / (4 * ps.cg)), block(kPanelThreads);
-#define ASLP_BN_FWD_PANEL(CG, SLOTS)                                                                                                       \
-    case CG * 100 + SLOTS:                                                                                                                \
-      hipLaunchKernelGGL((bn_forward_panel<CG, SLOTS>), grid, block, 0, cur_stream(), in, d.stride, out, out_stride, xhat, xhat_stride, scale, \
-                         shift, mean, inv_std, acc_means, acc_vars, invB, var_floor, d.rows, act_out, act_stride);                          \
-      break;
-    switch (ps.cg * 100 + ps.slots) {
-      ASLP_BN_FWD_PANEL(4, 4) ASLP_BN_FWD_PANEL(4, 8) ASLP_BN_FWD_PANEL(4, 16)
-    }
-#undef ASLP_BN_FWD_PANEL
+  if (bp.path == 1) {
+    const dim3 grid(d.cols / (4 * kPanelCG));
+    with_slots(bp.slots, [&](auto S) {
+      hipLaunchKernelGGL((bn_forward_panel<kPanelCG, decltype(S)::value>), grid, block, 0, cur_stream(), in, d.stride, out, out_stride, xhat, xhat_stride,
+                         scale, shift, mean, inv_std, acc_means, acc_vars, invB, var_floor, d.rows, act_out, act_stride);
+    });
     check_launch("bn_forward_panel");
     return;
   }
@@ -1373,11 +1344,10 @@ int aslp_bn_forward_stats_p(const float *in, MatrixDim d, float *out, int out_st
   if (!out && !act_out) { set_error("aslp_bn_forward_stats: no output"); return 0; }
   if (groups != (d.rows + 31) / 32 || stats_ld < d.cols) { set_error("aslp_bn_forward_stats: statistics layout does not match the matrix"); return 0; }
   static const bool off = [] { const char *e = getenv("ASLP_BN_FROM_STATS"); return e && e[0] == '0'; }();   // A/B switch
-  const bool vec = d.cols % 4 == 0 && d.stride % 4 == 0 && (!out || (out_stride % 4 == 0 && aligned16(out))) &&
-                   (!act_out || (act_stride % 4 == 0 && aligned16(act_out))) && aligned16(in) && aligned16(mean) && aligned16(inv_std) &&
-                   aligned16(scale) && aligned16(shift);
+  const bool vec = d.cols % 4 == 0 && vec_ok(in, d.stride) && (!out || vec_ok(out, out_stride)) && (!act_out || vec_ok(act_out, act_stride)) && vec_ok(mean) &&
+                   vec_ok(inv_std) && vec_ok(scale) && vec_ok(shift);
   // the shapes the backward pass serves without a stored normalised copy (it recomputes xhat from `in` and the batch mean)
-  if (off || !vec || d.cols % kCoopCols != 0 || !bn_panel_shape(d.rows, d.cols).cg) return 0;
+  if (off || !vec || d.cols % kCoopCols != 0 || !bn_panel_shape(d.rows, d.cols)) return 0;
   const int P = d.cols / kCoopCols;
   int Q = 1;
   while (Q < 8 && P * Q * 2 <= 1024 && (d.rows + 2 * Q - 1) / (2 * Q) >= 64) Q *= 2;   // ~4 workgroups per CU at most, >= 64 rows each
@@ -1415,17 +1385,21 @@ static void bn_backward_impl(MatrixDim d, const float *out_diff, int od_stride, 
                              aslp_planes_out *diff_out = nullptr) {
   if (diff_out) { diff_out->nparts = 0; diff_out->planes_written = 0; }
   if (d.rows <= 0 || d.cols <= 0) return;
-  const bool y_ok = !act_y || (aligned16(act_y) && act_stride % 4 == 0);
+  const bool y_ok = !act_y || vec_ok(act_y, act_stride);
   const bool recompute = xhat == nullptr;
   if (recompute && (!in || !mean)) { set_error("aslp_bn_backward: without a normalised copy (xhat == NULL) the layer input and the batch mean are needed"); return; }
-  const bool panel_ok = od_stride % 4 == 0 && (!in_diff || (id_stride % 4 == 0 && aligned16(in_diff))) && aligned16(out_diff) && aligned16(inv_std) && y_ok &&
-                        (recompute ? (d.stride % 4 == 0 && aligned16(in) && aligned16(mean)) : (xhat_stride % 4 == 0 && aligned16(xhat)));
-  const PanelShape ps = panel_ok ? bn_panel_shape(d.rows, d.cols) : PanelShape{0, 0};
-  if (!ps.cg && recompute) { set_error("aslp_bn_backward: xhat == NULL is only served by the single-launch panel path (check aslp_bn_panel_supported)"); return; }
-  const CoopShape cs = ps.cg ? bn_coop_shape(d.rows, d.cols) : CoopShape{0, 0};
-  if (cs.q && coop_state().inbox) {
+  const bool panel_ok = vec_ok(out_diff, od_stride) && (!in_diff || vec_ok(in_diff, id_stride)) && vec_ok(inv_std) && y_ok &&
+                        (recompute ? (vec_ok(in, d.stride) && vec_ok(mean)) : vec_ok(xhat, xhat_stride));
+  const BnPath bp = bn_path_for(d.rows, d.cols, panel_ok);
+  if (!bp.path && recompute) { set_error("aslp_bn_backward: xhat == NULL is only served by the single-launch panel path (check aslp_bn_panel_supported)"); return; }
+  const dim3 block(kPanelThreads);
+  // the instantiation for (slots, act_y != NULL, recompute): f(SLOTS, HAS_Y, RECOMPUTE) as integral constants
+  auto with_instantiation = [&](auto &&f) {
+    with_slots(bp.slots, [&](auto S) { with_flag(act_y != nullptr, [&](auto Y) { with_flag(recompute, [&](auto R) { f(S, Y, R); }); }); });
+  };
+  if (bp.path == 2) {
     CoopState &st = coop_state();
-    const dim3 grid((d.cols / kCoopCols) * cs.q), block(kPanelThreads);
+    const dim3 grid((d.cols / kCoopCols) * bp.q);
     // in_diff's planes from this launch when all its workgroups are resident at once (they wait for each other's maxima: one per CU is
     // what the shape was chosen for), else the maxima for the conversion pass
     S16Out po = {nullptr, nullptr, 0, nullptr, nullptr};
@@ -1440,36 +1414,21 @@ static void bn_backward_impl(MatrixDim d, const float *out_diff, int od_stride, 
     }
     float *max_parts = (!po.hi && diff_out && diff_out->parts && in_diff && (int)grid.x <= kS16MaxParts) ? diff_out->parts : nullptr;
     if (max_parts) diff_out->nparts = (int)grid.x;
-#define ASLP_BN_BWD_CL(SLOTS, Y, RC)                                                                                                           \
-    hipLaunchKernelGGL((bn_backward_coop<SLOTS, Y, RC>), grid, block, 0, cur_stream(), out_diff, od_stride, xhat, xhat_stride, scale, shift, inv_std, \
-                       dscale, dshift, momentum, -learn_rate, step, in_diff, id_stride, d.rows, act_y, act_stride, in, d.stride, mean, cs.q, st.inbox, st.err, \
-                       max_parts, po, st.gmax, token)
-#define ASLP_BN_BWD_COOP(SLOTS)                                                                      \
-    case SLOTS:                                                                                      \
-      if (act_y) { if (recompute) ASLP_BN_BWD_CL(SLOTS, true, true); else ASLP_BN_BWD_CL(SLOTS, true, false); }     \
-      else { if (recompute) ASLP_BN_BWD_CL(SLOTS, false, true); else ASLP_BN_BWD_CL(SLOTS, false, false); }         \
-      break;
-    switch (cs.slots) { ASLP_BN_BWD_COOP(4) ASLP_BN_BWD_COOP(8) ASLP_BN_BWD_COOP(16) }
-#undef ASLP_BN_BWD_COOP
-#undef ASLP_BN_BWD_CL
+    with_instantiation([&](auto S, auto Y, auto R) {
+      hipLaunchKernelGGL((bn_backward_coop<decltype(S)::value, decltype(Y)::value, decltype(R)::value>), grid, block, 0, cur_stream(), out_diff, od_stride, xhat,
+                         xhat_stride, scale, shift, inv_std, dscale, dshift, momentum, -learn_rate, step, in_diff, id_stride, d.rows, act_y, act_stride, in,
+                         d.stride, mean, bp.q, st.inbox, st.err, max_parts, po, st.gmax, token);
+    });
     check_launch("bn_backward_coop");
     return;
   }
-  if (ps.cg) {
-    const dim3 grid(d.cols / (4 * ps.cg)), block(kPanelThreads);
-#define ASLP_BN_BWD_LAUNCH(CG, SLOTS, Y, RC)                                                                                                      \
-    hipLaunchKernelGGL((bn_backward_panel<CG, SLOTS, Y, RC>), grid, block, 0, cur_stream(), out_diff, od_stride, xhat, xhat_stride, scale, shift,    \
-                       inv_std, dscale, dshift, momentum, -learn_rate, step, in_diff, id_stride, d.rows, act_y, act_stride, in, d.stride, mean)
-#define ASLP_BN_BWD_PANEL(CG, SLOTS)                                                             \
-    case CG * 100 + SLOTS:                                                                      \
-      if (act_y) { if (recompute) ASLP_BN_BWD_LAUNCH(CG, SLOTS, true, true); else ASLP_BN_BWD_LAUNCH(CG, SLOTS, true, false); }   \
-      else { if (recompute) ASLP_BN_BWD_LAUNCH(CG, SLOTS, false, true); else ASLP_BN_BWD_LAUNCH(CG, SLOTS, false, false); }       \
-      break;
-    switch (ps.cg * 100 + ps.slots) {
-      ASLP_BN_BWD_PANEL(4, 4) ASLP_BN_BWD_PANEL(4, 8) ASLP_BN_BWD_PANEL(4, 16)
-    }
-#undef ASLP_BN_BWD_PANEL
-#undef ASLP_BN_BWD_LAUNCH
+  if (bp.path == 1) {
+    const dim3 grid(d.cols / (4 * kPanelCG));
+    with_instantiation([&](auto S, auto Y, auto R) {
+      hipLaunchKernelGGL((bn_backward_panel<kPanelCG, decltype(S)::value, decltype(Y)::value, decltype(R)::value>), grid, block, 0, cur_stream(), out_diff,
+                         od_stride, xhat, xhat_stride, scale, shift, inv_std, dscale, dshift, momentum, -learn_rate, step, in_diff, id_stride, d.rows, act_y,
+                         act_stride, in, d.stride, mean);
+    });
     check_launch("bn_backward_panel");
     bn_in_diff_one_row(d, in_diff);
     return;
@@ -1477,13 +1436,12 @@ static void bn_backward_impl(MatrixDim d, const float *out_diff, int od_stride, 
   float *s12 = static_cast<float *>(scratch(kScratchReduce2, sizeof(float) * 3 * (size_t)d.cols));
   if (!s12) return;
   float *scale_used = s12 + 2 * (size_t)d.cols;
+  const bool stats_vec = vec_ok(out_diff, od_stride) && vec_ok(xhat, xhat_stride) && y_ok;
   colreduce<2, float>("bn_backward.stats", d.rows, d.cols, BnBwdF{out_diff, od_stride, xhat, xhat_stride, act_y, act_stride},
-                      BnBwdG{momentum, dscale, dshift, s12, s12 + d.cols, scale, shift, scale_used, -learn_rate, step},
-                      aligned16(out_diff) && od_stride % 4 == 0 && aligned16(xhat) && xhat_stride % 4 == 0 && y_ok);
+                      BnBwdG{momentum, dscale, dshift, s12, s12 + d.cols, scale, shift, scale_used, -learn_rate, step}, stats_vec);
   if (!in_diff) return;
   long n = (long)d.rows * d.cols;
-  bool vec = d.cols % 4 == 0 && od_stride % 4 == 0 && xhat_stride % 4 == 0 && id_stride % 4 == 0 && aligned16(out_diff) &&
-             aligned16(xhat) && aligned16(in_diff) && aligned16(inv_std) && aligned16(s12) && y_ok;
+  const bool vec = d.cols % 4 == 0 && stats_vec && vec_ok(in_diff, id_stride) && vec_ok(inv_std) && vec_ok(s12);
   if (vec) hipLaunchKernelGGL((bn_backward_kernel<true>), dim3(grid_for(n / 4)), dim3(kBlock), 0, cur_stream(), out_diff, od_stride, xhat, xhat_stride, scale_used, inv_std, s12, s12 + d.cols, in_diff, id_stride, d.rows, d.cols, act_y, act_stride);
   else hipLaunchKernelGGL((bn_backward_kernel<false>), dim3(grid_for(n)), dim3(kBlock), 0, cur_stream(), out_diff, od_stride, xhat, xhat_stride, scale_used, inv_std, s12, s12 + d.cols, in_diff, id_stride, d.rows, d.cols, act_y, act_stride);
   check_launch("bn_backward");
@@ -1511,19 +1469,13 @@ void aslp_bn_backward_step_p(MatrixDim d, const float *out_diff, int od_stride, 
 }
 // 1: a [rows x cols] batch is served by the single-launch panel kernels (given 16-byte aligned operands), which need no
 // normalised copy of the input: pass xhat = NULL to the forward and backward entry points and save its 8.4 MB each way
-int aslp_bn_panel_supported(int rows, int cols) { return bn_panel_shape(rows, cols).cg != 0 ? 1 : 0; }
+int aslp_bn_panel_supported(int rows, int cols) { return bn_panel_shape(rows, cols) != 0 ? 1 : 0; }
 // the choice aslp_bn_forward_act / bn_backward_impl make for 16-byte aligned operands, without a launch (tests name their instantiation by it)
 int aslp_bn_path(int rows, int cols, int *q, int *slots) {
-  int path = 0, qq = 0, sl = 0;
-  if (rows > 0 && cols > 0 && cols % 4 == 0) {
-    const PanelShape ps = bn_panel_shape(rows, cols);
-    const CoopShape cs = ps.cg ? bn_coop_shape(rows, cols) : CoopShape{0, 0};
-    if (cs.q && coop_state().inbox) { path = 2; qq = cs.q; sl = cs.slots; }
-    else if (ps.cg) { path = 1; qq = 1; sl = ps.slots; }
-  }
-  if (q) *q = qq;
-  if (slots) *slots = sl;
-  return path;
+  const BnPath bp = bn_path_for(rows, cols, rows > 0 && cols > 0);
+  if (q) *q = bp.q;
+  if (slots) *slots = bp.slots;
+  return bp.path;
 }
 void aslp_bn_backward(const float *in, MatrixDim d, const float *out_diff, int od_stride, float *xhat, int xhat_stride, const float *scale,
                       const float *mean, const float *inv_std, float *dscale, float *dshift, float momentum, float *in_diff, int id_stride) {
