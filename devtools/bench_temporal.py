@@ -65,3 +65,22 @@ def rc_ops():
 s2 = timeit_ev(rc_ops, reps=5)
 print("RowConvolution ops level (3 launches: forward; in-diff + tap partials; finish + update): %.1f us, algorithmic (7 tensor passes) %.1f GB/s = %.2f of 8 TB/s" % (
     s2 * 1e6, 4 * D * T * S * 7 / s2 / 1e9, 4 * D * T * S * 7 / s2 / 8e12))
+
+# ---- optional (--plain): the plain kernels, which the shapes above never reach, at one shape each (same T, S, D; ops level)
+if "--plain" in sys.argv[1:]:
+    K2 = 40      # more than 32 taps: rowconv_fwd; rowconv_bwd, rowconv_wgrad1<64> + rowconv_wgrad2 and the separate momentum + SGD step
+    assert aslp.lib.aslp_rowconv_path(D, K2, D, D, D, None, None, None) == 0
+    w2 = torch.randn(D * (K2 + 1), device=dev) * 0.1; wd2 = torch.zeros_like(w2); wc2 = torch.zeros_like(w2)
+    def rc_plain():
+        aslp.ops.rowconv_forward(o2, x2, w2, sl, K2)
+        aslp.ops.rowconv_backward(idf2, wd2, x2, od2, w2, sl, K2, wc2, 0.9, 1e-5)
+    s3 = timeit_ev(rc_plain, reps=3)
+    print("RowConvolution plain kernels K=%d (forward; in-diff; tap gradients in two stages; step): %.1f us" % (K2, s3 * 1e6))
+    P2 = F2 = 120   # 241 taps: fsmn_filter forward and reversed, fsmn_coef_grad1 + fsmn_coef_grad2 and the separate step
+    assert aslp.lib.aslp_fsmn_path(D, P2, F2, T, D, 0) == 0 and aslp.lib.aslp_fsmn_path(D, P2, F2, T, D, 1) == 0
+    coef2 = torch.randn(P2 + F2 + 1, D, device=dev) * 0.05; corr2 = torch.zeros_like(coef2)
+    def fsmn_plain():
+        aslp.ops.fsmn_forward(o, x, coef2, P2, F2)
+        aslp.ops.fsmn_backward(idf, corr2, coef2, x, od, P2, F2, 0.0, 1e-5)
+    s4 = timeit_ev(fsmn_plain)
+    print("CompactFsmn  plain kernels %d+%d taps (forward; tap gradients in two stages; in-diff; step): %.1f us" % (P2, F2, s4 * 1e6))

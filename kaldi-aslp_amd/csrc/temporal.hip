@@ -20,8 +20,19 @@
 // fixed-order sum over the chunks, the clip and the SGD step.
 //
 // Shapes outside what these serve (more than 32 taps in RowConvolution, odd widths, filters too long for the LDS tile) run on the
-// simpler kernels kept at the end of each section: lanes along the feature dimension, a register window over TT frames per thread,
-// tap gradients by a two-stage reduction.
+// plain kernels: lanes along the feature dimension, a register window over TT frames per thread, tap gradients by a two-stage
+// reduction.
+//
+// Each rule is written once, as a __device__ __forceinline__ part or a host helper:
+//   plain kernels       row_or_zero (the guarded row fetch, all boundary rules), window_filter (taps, multiply-adds and the slide), sum_chunks
+//                       (the ascending sum of the second stages), clip_to and sgd_step (shared with the two finishing kernels, whose
+//                       summation orders are their own); host: window_launch
+//   streaming RowConv   rc_place + rc_lane (what a lane owns, its base pointers and row strides), rc_load_taps; host: rc_grid, and
+//                       rowconv_ring + with_ring, the only two lists of the instantiations
+//   CompactFsmn tiles   stage_load + stage_store (every row that enters LDS), ring_tap / ring_block8 / ring_sweep (the read-ahead ring loop of
+//                       the filter and of the tap-gradient sweep), fsmn_tile_rows / fsmn_tap_rows (the LDS layout); host: allow_lds_budget
+#include <type_traits>
+
 #include "aslp_kernels.h"
 #include "common.h"
 #include "scratch.h"
@@ -31,34 +42,60 @@ namespace {
 
 constexpr int TT = 8;  // frames per thread
 
+// ---- parts of the plain kernels ------------------------------------------------------------------------
+// Element of logical row r of a column (`col`: the column in row 0; rows are `stride` elements apart), 0 outside [0, n).  REPEAT_LAST: rows
+// past n - 1 repeat row n - 1 (RowConvolution's input: frames past a stream's length repeat its last frame, row-convolution.cc:118-126;
+// an empty stream reads 0).
+template <bool REPEAT_LAST>
+__device__ __forceinline__ float row_or_zero(const float *__restrict__ col, long stride, int r, int n) {
+  if (REPEAT_LAST) r = min(r, n - 1);
+  return (r >= 0 && (REPEAT_LAST || r < n)) ? col[(long)r * stride] : 0.0f;
+}
+
+// The register-window filter of a thread's TT frames t0 ... t0 + TT - 1:
+//   FORWARD   store(t0 + u, sum_j tap(j) row(t0 + u + j - pad))     the window slides towards later rows
+//   otherwise store(t0 + u, sum_k tap(k) row(t0 + u - k))           ... towards earlier ones
+// Per output a sequential multiply-add in tap order; every row is fetched once per thread.
+template <bool FORWARD, int UNROLL, class Row, class Tap, class Store>
+__device__ __forceinline__ void window_filter(int t0, int ntaps, int pad, Row row, Tap tap, Store store) {
+  float acc[TT], win[TT];
+#pragma unroll
+  for (int u = 0; u < TT; u++) { acc[u] = 0.0f; win[u] = row(t0 + u - pad); }
+#pragma unroll UNROLL
+  for (int j = 0; j < ntaps; j++) {
+    const float c = tap(j);
+#pragma unroll
+    for (int u = 0; u < TT; u++) acc[u] += win[u] * c;
+#pragma unroll
+    for (int u = 0; u < TT - 1; u++) win[FORWARD ? u : TT - 1 - u] = win[FORWARD ? u + 1 : TT - 2 - u];   // the slide, by one row
+    win[FORWARD ? TT - 1 : 0] = row(FORWARD ? t0 + TT + j - pad : t0 - 1 - j);
+  }
+#pragma unroll
+  for (int u = 0; u < TT; u++) store(t0 + u, acc[u]);
+}
+// the first frame of the thread's window (the grid: window_launch)
+__device__ __forceinline__ int window_t0() { return (blockIdx.y * (kBlock / kWave) + threadIdx.y) * TT; }
+
+// sum over the chunks, ascending, of partial[chunk][idx] (n elements per chunk)
+__device__ __forceinline__ float sum_chunks(const float *__restrict__ partial, long n, long idx, int chunks) {
+  float s = 0.0f;
+#pragma unroll 8
+  for (int c = 0; c < chunks; c++) s += partial[(long)c * n + idx];
+  return s;
+}
+__device__ __forceinline__ float clip_to(float s, float clip) { return clip > 0.0f ? fminf(fmaxf(s, -clip), clip) : s; }
+__device__ __forceinline__ float sgd_step(float w, float lr, float c) { return w + -lr * c; }
+
 // ---- CompactFsmn ---------------------------------------------------------------------------------------
 // out[t][d] = src[t][d] + sum_j coef[row(j)][d] * src[t + j - pad][d], rows outside [0,T) count as 0.
 // forward: row(j) = j, pad = P.  in-diff: row(j) = C-1-j, pad = F (the reversed filter, cfsmn.h:232-246).
 __global__ void __launch_bounds__(kBlock) fsmn_filter(float *__restrict__ out, int ldo, const float *__restrict__ src, int lds,
                                                       const float *__restrict__ coef, int ldc, int D, int C, int pad, int reverse, int T) {
-  const int d = blockIdx.x * kWave + threadIdx.x;
-  const int t0 = (blockIdx.y * (kBlock / kWave) + threadIdx.y) * TT;
+  const int d = blockIdx.x * kWave + threadIdx.x, t0 = window_t0();
   if (d >= D || t0 >= T) return;
-  float acc[TT], win[TT];
-#pragma unroll
-  for (int u = 0; u < TT; u++) {
-    acc[u] = 0.0f;
-    const int r = t0 + u - pad;
-    win[u] = (r >= 0 && r < T) ? src[(long)r * lds + d] : 0.0f;
-  }
-#pragma unroll 4
-  for (int j = 0; j < C; j++) {
-    const float c = coef[(long)(reverse ? C - 1 - j : j) * ldc + d];
-#pragma unroll
-    for (int u = 0; u < TT; u++) acc[u] += win[u] * c;
-#pragma unroll
-    for (int u = 0; u < TT - 1; u++) win[u] = win[u + 1];
-    const int r = t0 + TT + j - pad;
-    win[TT - 1] = (r >= 0 && r < T) ? src[(long)r * lds + d] : 0.0f;
-  }
-#pragma unroll
-  for (int u = 0; u < TT; u++)
-    if (t0 + u < T) out[(long)(t0 + u) * ldo + d] = src[(long)(t0 + u) * lds + d] + acc[u];
+  window_filter<true, 4>(
+      t0, C, pad, [=](int r) { return row_or_zero<false>(src + d, lds, r, T); }, [=](int j) { return coef[(long)(reverse ? C - 1 - j : j) * ldc + d]; },
+      [=](int t, float a) { if (t < T) out[(long)t * ldo + d] = src[(long)t * lds + d] + a; });
 }
 
 // stage 1 of the tap gradient: partial[chunk][i][d] = sum_{t in chunk} in[t + i - P][d] * od[t][d]
@@ -80,74 +117,33 @@ __global__ void __launch_bounds__(kBlock) fsmn_coef_grad2(float *__restrict__ co
   const long n = (long)C * D;
   for (long idx = blockIdx.x * (long)blockDim.x + threadIdx.x; idx < n; idx += (long)gridDim.x * blockDim.x) {
     const int i = idx / D, d = idx - (long)i * D;
-    float s = 0.0f;
-#pragma unroll 8
-    for (int c = 0; c < chunks; c++) s += partial[((long)c * C + i) * D + d];
-    if (clip > 0.0f) s = fminf(fmaxf(s, -clip), clip);
-    corr[(long)i * ldc + d] = s;  // beta 0: no momentum in the reference (cfsmn.h:219)
+    corr[(long)i * ldc + d] = clip_to(sum_chunks(partial, n, idx, chunks), clip);  // beta 0: no momentum in the reference (cfsmn.h:219)
   }
 }
 
 // ---- RowConvolution ----------------------------------------------------------------------------------------
-// rows are t*S + s; frames past the stream's length repeat its last frame (row-convolution.cc:118-126)
-__global__ void __launch_bounds__(kBlock) rowconv_fwd(float *__restrict__ out, int ldo, const float *__restrict__ in, int ldi,
-                                                      const float *__restrict__ w, int D, int K, int T, int S,
-                                                      const int32_t *__restrict__ seq_len) {
-  const int d = blockIdx.x * kWave + threadIdx.x;
-  const int s = blockIdx.z;
-  const int t0 = (blockIdx.y * (kBlock / kWave) + threadIdx.y) * TT;
+// rows are t*S + s.  Both plain passes of a stream of length L = min(seq_len[s], T), frames past L stored as 0:
+//   FORWARD   out[t] = sum_{k <= K} w[d][k] in[min(t + k, L - 1)]: frames past the length repeat its last frame (row-convolution.cc:118-126)
+//   otherwise in_diff[t] = sum_{k <= min(K,t)} w[d][k] od[t - k], od 0 past L: the part of the diff that fell on the replicated tail
+//             frames is dropped, as in the reference (:168-174)
+template <bool FORWARD>
+__device__ __forceinline__ void rowconv_window(float *__restrict__ dst, int ldd, const float *__restrict__ src, int lds, const float *__restrict__ w,
+                                               int D, int K, int T, int S, const int32_t *__restrict__ seq_len) {
+  const int d = blockIdx.x * kWave + threadIdx.x, s = blockIdx.z, t0 = window_t0();
   if (d >= D || t0 >= T) return;
   const int L = min(seq_len[s], T);
-  float acc[TT], win[TT];
-#pragma unroll
-  for (int u = 0; u < TT; u++) {
-    acc[u] = 0.0f;
-    const int r = min(t0 + u, L - 1);
-    win[u] = r >= 0 ? in[((long)r * S + s) * ldi + d] : 0.0f;
-  }
-  for (int k = 0; k <= K; k++) {
-    const float c = w[(long)d * (K + 1) + k];
-#pragma unroll
-    for (int u = 0; u < TT; u++) acc[u] += c * win[u];
-#pragma unroll
-    for (int u = 0; u < TT - 1; u++) win[u] = win[u + 1];
-    const int r = min(t0 + TT + k, L - 1);
-    win[TT - 1] = r >= 0 ? in[((long)r * S + s) * ldi + d] : 0.0f;
-  }
-#pragma unroll
-  for (int u = 0; u < TT; u++)
-    if (t0 + u < T) out[((long)(t0 + u) * S + s) * ldo + d] = (t0 + u < L) ? acc[u] : 0.0f;  // frames past the end stay 0
+  window_filter<FORWARD, 1>(
+      t0, K + 1, 0, [=](int r) { return row_or_zero<FORWARD>(src + (long)s * lds + d, (long)S * lds, r, L); },
+      [=](int k) { return w[(long)d * (K + 1) + k]; },
+      [=](int t, float a) { if (t < T) dst[((long)t * S + s) * ldd + d] = t < L ? a : 0.0f; });
 }
-
-// in_diff[t] = sum_{k <= min(K,t)} w[d][k] * od[t-k] for t < L, 0 beyond; the part of the diff that fell
-// on the replicated tail frames is dropped, as in the reference (:168-174)
+__global__ void __launch_bounds__(kBlock) rowconv_fwd(float *__restrict__ out, int ldo, const float *__restrict__ in, int ldi,
+                                                      const float *__restrict__ w, int D, int K, int T, int S, const int32_t *__restrict__ seq_len) {
+  rowconv_window<true>(out, ldo, in, ldi, w, D, K, T, S, seq_len);
+}
 __global__ void __launch_bounds__(kBlock) rowconv_bwd(float *__restrict__ in_diff, int ldid, const float *__restrict__ od, int ldod,
-                                                      const float *__restrict__ w, int D, int K, int T, int S,
-                                                      const int32_t *__restrict__ seq_len) {
-  const int d = blockIdx.x * kWave + threadIdx.x;
-  const int s = blockIdx.z;
-  const int t0 = (blockIdx.y * (kBlock / kWave) + threadIdx.y) * TT;
-  if (d >= D || t0 >= T) return;
-  const int L = min(seq_len[s], T);
-  float acc[TT], win[TT];
-#pragma unroll
-  for (int u = 0; u < TT; u++) {
-    acc[u] = 0.0f;
-    const int r = t0 + u;
-    win[u] = r < L ? od[((long)r * S + s) * ldod + d] : 0.0f;
-  }
-  for (int k = 0; k <= K; k++) {
-    const float c = w[(long)d * (K + 1) + k];
-#pragma unroll
-    for (int u = 0; u < TT; u++) acc[u] += c * win[u];
-#pragma unroll
-    for (int u = TT - 1; u > 0; u--) win[u] = win[u - 1];
-    const int r = t0 - 1 - k;
-    win[0] = r >= 0 && r < L ? od[((long)r * S + s) * ldod + d] : 0.0f;
-  }
-#pragma unroll
-  for (int u = 0; u < TT; u++)
-    if (t0 + u < T) in_diff[((long)(t0 + u) * S + s) * ldid + d] = (t0 + u < L) ? acc[u] : 0.0f;
+                                                      const float *__restrict__ w, int D, int K, int T, int S, const int32_t *__restrict__ seq_len) {
+  rowconv_window<false>(in_diff, ldid, od, ldod, w, D, K, T, S, seq_len);
 }
 
 // partial[chunk][k][d] = sum over the streams s and the frames t of the chunk (t < L_s) of
@@ -201,10 +197,7 @@ __global__ void __launch_bounds__(kBlock) rowconv_wgrad2(float *__restrict__ w_d
   const long n = (long)D * (K + 1);
   for (long idx = blockIdx.x * (long)blockDim.x + threadIdx.x; idx < n; idx += (long)gridDim.x * blockDim.x) {
     const int k = idx / D, d = idx - (long)k * D;
-    float s = 0.0f;
-#pragma unroll 8
-    for (int c = 0; c < chunks; c++) s += partial[((long)c * (K + 1) + k) * D + d];
-    w_diff[(long)d * (K + 1) + k] = s;
+    w_diff[(long)d * (K + 1) + k] = sum_chunks(partial, n, idx, chunks);
   }
 }
 
@@ -217,39 +210,48 @@ constexpr int kRcStreams = kBlock / kWave;   // streams per workgroup (one per w
 // (ids go round-robin over the 8 XCDs)
 struct RcPlace { int chunk, dtile, sgroup; bool valid; };
 __device__ __forceinline__ RcPlace rc_place(int nchunks, int dtiles, int nstrips) {
-  const int id = blockIdx.x, xcd = id & 7, j = id >> 3;
-  RcPlace p;
-  p.chunk = j % nchunks;
-  const int strip = (j / nchunks) * 8 + xcd;
-  p.valid = strip < nstrips;
-  p.dtile = strip % dtiles;
-  p.sgroup = strip / dtiles;
-  return p;
+  const int id = blockIdx.x, xcd = id & 7, j = id >> 3, strip = (j / nchunks) * 8 + xcd;
+  return {j % nchunks, strip % dtiles, strip / dtiles, strip < nstrips};
+}
+// ... -> what a lane of a workgroup with a strip owns: the column pair d0, d0 + 1 of stream s (live: both exist)
+struct RcLane {
+  int d0, s, S; bool live;
+  // the lane's pair in frame 0 of its stream, for a matrix with leading dimension ld, and the distance from a frame to the next
+  template <class T> __device__ __forceinline__ T *col(T *m, int ld) const { return m + (long)s * ld + d0; }
+  __device__ __forceinline__ long stride(int ld) const { return (long)S * ld; }
+};
+__device__ __forceinline__ RcLane rc_lane(const RcPlace p, int D, int S) {
+  const int d0 = (p.dtile * kWave + threadIdx.x) * 2, s = p.sgroup * kRcStreams + threadIdx.y;
+  return {d0, s, S, d0 < D && s < S};
+}
+// the taps of the lane's two columns, one pair per ring slot; EXACT: KP == K + 1 (no tap is tested against K), else the slots past K are 0
+template <int KP, bool EXACT>
+__device__ __forceinline__ void rc_load_taps(f2 (&wr)[KP], const float *__restrict__ w, int d0, int K) {
+#pragma unroll
+  for (int k = 0; k < KP; k++) wr[k] = (EXACT || k <= K) ? f2{w[(long)d0 * (K + 1) + k], w[(long)(d0 + 1) * (K + 1) + k]} : f2{0.f, 0.f};
 }
 
-// out[t] = sum_{k <= K} w[:,k] in[min(t + k, L - 1)] for t < L, 0 beyond.  KP >= K + 1 is the ring length; EXACT: KP == K + 1 (no
-// tap is tested against K).  Row r meets tap k for output t = r - k, which lives in ring slot (t - ta) mod KP: static indices once
-// the row loop is unrolled by KP.  An output is taken out of the ring KP - 1 rows after its own row (taps beyond K are not applied).
+// out[t] = sum_{k <= K} w[:,k] in[min(t + k, L - 1)] for t < L, 0 beyond.  KP >= K + 1 is the ring length.  Row r meets tap k for output
+// t = r - k, which lives in ring slot (t - ta) mod KP: static indices once the row loop is unrolled by KP.  An output is taken out of the
+// ring KP - 1 rows after its own row (taps beyond K are not applied).
 template <int KP, bool EXACT>
 __global__ void __launch_bounds__(kBlock) rowconv_fwd_stream(float *__restrict__ out, int ldo, const float *__restrict__ in, int ldi,
                                                              const float *__restrict__ w, int D, int K, int T, int S,
                                                              const int32_t *__restrict__ seq_len, int tc, int nchunks, int dtiles, int nstrips) {
   const RcPlace pl = rc_place(nchunks, dtiles, nstrips);
   if (!pl.valid) return;
-  const int d0 = (pl.dtile * kWave + threadIdx.x) * 2, s = pl.sgroup * kRcStreams + threadIdx.y;
-  if (d0 >= D || s >= S) return;
+  const RcLane ln = rc_lane(pl, D, S);
+  if (!ln.live) return;
   const int ta = pl.chunk * tc, tb = min(T, ta + tc);
-  const int L = min(seq_len[s], T), tv = min(tb, L);
-  const long rs_in = (long)S * ldi, rs_out = (long)S * ldo;
-  float *op = out + (long)s * ldo + d0;
+  const int L = min(seq_len[ln.s], T), tv = min(tb, L);
+  const long rs_in = ln.stride(ldi), rs_out = ln.stride(ldo);
+  float *op = ln.col(out, ldo);
   if (tv > ta) {
-    const float *ip = in + (long)s * ldi + d0;
+    const float *ip = ln.col(in, ldi);
     f2 wr[KP], acc[KP];
+    rc_load_taps<KP, EXACT>(wr, w, ln.d0, K);
 #pragma unroll
-    for (int k = 0; k < KP; k++) {
-      wr[k] = (EXACT || k <= K) ? f2{w[(long)d0 * (K + 1) + k], w[(long)(d0 + 1) * (K + 1) + k]} : f2{0.f, 0.f};
-      acc[k] = f2{0.f, 0.f};
-    }
+    for (int k = 0; k < KP; k++) acc[k] = f2{0.f, 0.f};
     const int rend = tv + KP - 1;
     for (int r0 = ta; r0 < rend; r0 += KP) {
       f2 x[KP];
@@ -282,22 +284,20 @@ __global__ void __launch_bounds__(kBlock) rowconv_bwd_fused(float *__restrict__ 
   __shared__ float red[kRcStreams - 1][KP][kRcCols];
   const RcPlace pl = rc_place(nchunks, dtiles, nstrips);
   if (!pl.valid) return;   // (the whole workgroup)
+  const RcLane ln = rc_lane(pl, D, S);
   const int x = threadIdx.x, y = threadIdx.y;
-  const int d0 = (pl.dtile * kWave + x) * 2, s = pl.sgroup * kRcStreams + y;
-  const bool live = d0 < D && s < S;
   f2 g[KP];
 #pragma unroll
   for (int k = 0; k < KP; k++) g[k] = f2{0.f, 0.f};
-  if (live) {
+  if (ln.live) {
     const int ra = pl.chunk * tc, rb = ra + tc;
-    const int L = min(seq_len[s], T), re = min(rb, L + K);
-    const long rs_in = (long)S * ldi, rs_od = (long)S * ldod, rs_id = (long)S * ldid;
-    float *dp = in_diff + (long)s * ldid + d0;
+    const int L = min(seq_len[ln.s], T), re = min(rb, L + K);
+    const long rs_in = ln.stride(ldi), rs_od = ln.stride(ldod), rs_id = ln.stride(ldid);
+    float *dp = ln.col(in_diff, ldid);
     if (re > ra && L > 0) {
-      const float *ip = in + (long)s * ldi + d0, *gp = od + (long)s * ldod + d0;
+      const float *ip = ln.col(in, ldi), *gp = ln.col(od, ldod);
       f2 wr[KP], o[KP];
-#pragma unroll
-      for (int k = 0; k < KP; k++) wr[k] = (EXACT || k <= K) ? f2{w[(long)d0 * (K + 1) + k], w[(long)(d0 + 1) * (K + 1) + k]} : f2{0.f, 0.f};
+      rc_load_taps<KP, EXACT>(wr, w, ln.d0, K);
       // rows ra - (KP - 1) ... ra - 1 in slots 0 ... KP - 2; row r of the loop goes to slot (KP - 1 + i) % KP
 #pragma unroll
       for (int j = 0; j < KP - 1; j++) {
@@ -338,8 +338,8 @@ __global__ void __launch_bounds__(kBlock) rowconv_bwd_fused(float *__restrict__ 
     for (int k = 0; k < KP; k++) { red[y - 1][k][2 * x] = g[k].x; red[y - 1][k][2 * x + 1] = g[k].y; }
   }
   __syncthreads();
-  if (y == 0 && d0 < D) {
-    float *pp = partial + ((long)pl.chunk * sgroups + pl.sgroup) * (K + 1) * D + d0;
+  if (y == 0 && ln.d0 < D) {
+    float *pp = partial + ((long)pl.chunk * sgroups + pl.sgroup) * (K + 1) * D + ln.d0;
 #pragma unroll
     for (int k = 0; k < KP; k++)
       if (EXACT || k <= K) {
@@ -374,7 +374,7 @@ __global__ void __launch_bounds__(kWave * kFinishWaves) rowconv_wgrad_finish(flo
   if (update) {
     const float c = mmt * w_corr[o] + s;
     w_corr[o] = c;
-    w[o] += -lr * c;
+    w[o] = sgd_step(w[o], lr, c);
   }
 }
 
@@ -386,6 +386,9 @@ __global__ void __launch_bounds__(kWave * kFinishWaves) rowconv_wgrad_finish(flo
 constexpr int kFsmnWaves = kBlock / kWave;   // 4
 constexpr int kFsmnFrames = kFsmnWaves * TT; // frames per tile: one block of TT per wave
 constexpr int kFsmnSpare = 3 * TT;           // rows behind every LDS region that read-ahead may touch (zeros or stale: never used)
+// the LDS layout at C taps, in rows of 64 floats: a region of source rows (the tile's frames and their C - 1 neighbours), the taps' region
+__host__ __device__ constexpr int fsmn_tile_rows(int C) { return kFsmnFrames + C - 1 + kFsmnSpare; }
+__host__ __device__ constexpr int fsmn_tap_rows(int C) { return C + kFsmnSpare; }
 
 // One tap against a ring window of N registers, with the ring position a COMPILE-TIME constant (a loop index inside `win[(u + jj) % N]` is
 // turned into selects by the compiler unless every level of the nest is unrolled; spelled out, it cannot be):
@@ -414,22 +417,61 @@ __device__ __forceinline__ void ring_block8(float (&acc)[8], float (&win)[8], co
   if (j0 + 7 < limit) ring_tap<7, 8>(acc, win, c[7], e[7]);
 }
 static_assert(TT == 8, "ring_block8 is written for windows of 8");
+// done(u, sum_{j < count} mul[j] rows[u + j]) for u < 8, j ascending: `mul` and `rows` are a thread's column of two LDS regions (row i at
+// [i * kWave]).  Sums and window are locals here and leave through `done` (handed in by reference they cost fsmn_backward_fused 8 registers
+// and the forward + backward pair 0.6 of 25.2 us: profiles/temporal_parts_timing.txt).  The window is a ring: step j reads elements j ... j + 7, element e sits in slot e % 8, and the slot of element j takes j + 8.
+// Multipliers and incoming elements of a block of 8 steps are read one block AHEAD (16 LDS reads in flight under 64 multiply-adds): with one
+// wave per SIMD nothing else hides an LDS read that is used the moment it is issued.  Reads past step count - 1 land in the regions' spare
+// rows -- kFsmnSpare of them behind each -- and are never used.
+template <class Done>
+__device__ __forceinline__ void ring_sweep(const float *mul, const float *rows, int count, Done done) {
+  float acc[TT], win[TT], cn[TT], en[TT];
+#pragma unroll
+  for (int u = 0; u < TT; u++) { acc[u] = 0.0f; win[u] = rows[u * kWave]; }
+#pragma unroll
+  for (int jj = 0; jj < TT; jj++) { cn[jj] = mul[jj * kWave]; en[jj] = rows[(TT + jj) * kWave]; }
+  for (int j0 = 0; j0 < count; j0 += TT) {
+    float c[TT], e[TT];
+#pragma unroll
+    for (int jj = 0; jj < TT; jj++) { c[jj] = cn[jj]; e[jj] = en[jj]; }
+#pragma unroll
+    for (int jj = 0; jj < TT; jj++) { cn[jj] = mul[(j0 + TT + jj) * kWave]; en[jj] = rows[(j0 + 2 * TT + jj) * kWave]; }
+    ring_block8(acc, win, c, e, j0, count);
+  }
+#pragma unroll
+  for (int u = 0; u < TT; u++) done(u, acc[u]);
+}
 
-// rows [r0, r0 + n) of a [T x D] matrix into an LDS tile of 64 columns (zeros outside the matrix; `spare` further rows of zeros), and -- with
-// taps != nullptr -- the C taps (reversed: tap j is coef row C - 1 - j) into theirs, by the whole workgroup.  Up to 26 rows and 16 taps per
-// thread and round (104 rows, 64 taps: the 100 rows of a 30 + 30-tap tile in one round); 32-bit element offsets from the scalar bases, one address register per
-// load -- the launchers check that they fit.
+// Staging, by the whole workgroup: LDS row i of a region of 64 columns holds row r0 + i of a [T x D] matrix for i < n (zero outside the
+// matrix and in columns past D).  A thread takes the rows i = i0 + u kFsmnWaves, u < U: stage_load brings them into registers, stage_store
+// puts those below n_lds (n, or n and spare rows of zeros behind them) into the region.  32-bit element offsets from the scalar bases, one
+// address register per load -- the launchers check that they fit.
+template <int U>
+__device__ __forceinline__ void stage_load(float (&v)[U], const float *__restrict__ src, int ld, int r0, int n, int T, bool col_ok, int d, int i0) {
+#pragma unroll
+  for (int u = 0; u < U; u++) {
+    const int i = i0 + u * kFsmnWaves, r = r0 + i;
+    v[u] = (col_ok && i < n && r >= 0 && r < T) ? src[(unsigned)(r * ld + d)] : 0.0f;
+  }
+}
+template <int U>
+__device__ __forceinline__ void stage_store(float *__restrict__ region, const float (&v)[U], int n_lds, int x, int i0) {
+#pragma unroll
+  for (int u = 0; u < U; u++) {
+    const int i = i0 + u * kFsmnWaves;
+    if (i < n_lds) region[i * kWave + x] = v[u];
+  }
+}
+// rows [r0, r0 + n) and `spare` rows of zeros into `tile`, and -- with taps != nullptr -- the C taps (reversed: tap j is coef row C - 1 - j)
+// into theirs.  Up to 26 rows and 16 taps per thread and round (104 rows, 64 taps: the 100 rows of a 30 + 30-tap tile in one round); every
+// load of a round is issued before its first LDS write.
 constexpr int kStageU = 26, kStageTapsU = 16;
 __device__ __forceinline__ void stage_rows_and_taps(float *__restrict__ tile, const float *__restrict__ src, int ld, int r0, int n, int spare, int T,
                                                     float *__restrict__ taps, const float *__restrict__ coef, int ldc, int C, bool reversed, bool col_ok, int d,
                                                     int x, int y) {
   for (int i0 = y, j0 = y; i0 < n + spare || (taps != nullptr && j0 < C); i0 += kFsmnWaves * kStageU, j0 += kFsmnWaves * kStageTapsU) {
     float v[kStageU], c[kStageTapsU];
-#pragma unroll
-    for (int u = 0; u < kStageU; u++) {
-      const int i = i0 + u * kFsmnWaves, r = r0 + i;
-      v[u] = (col_ok && i < n && r >= 0 && r < T) ? src[(unsigned)(r * ld + d)] : 0.0f;
-    }
+    stage_load(v, src, ld, r0, n, T, col_ok, d, i0);
     if (taps != nullptr) {
 #pragma unroll
       for (int u = 0; u < kStageTapsU; u++) {
@@ -437,129 +479,69 @@ __device__ __forceinline__ void stage_rows_and_taps(float *__restrict__ tile, co
         c[u] = (col_ok && j < C) ? coef[(unsigned)((reversed ? C - 1 - j : j) * ldc + d)] : 0.0f;
       }
     }
-#pragma unroll
-    for (int u = 0; u < kStageU; u++) {
-      const int i = i0 + u * kFsmnWaves;
-      if (i < n + spare) tile[i * kWave + x] = v[u];
-    }
-    if (taps != nullptr) {
-#pragma unroll
-      for (int u = 0; u < kStageTapsU; u++) {
-        const int j = j0 + u * kFsmnWaves;
-        if (j < C) taps[j * kWave + x] = c[u];
-      }
-    }
+    stage_store(tile, v, n + spare, x, i0);
+    if (taps != nullptr) stage_store(taps, c, C, x, j0);
   }
 }
-// out[t] = tile[t + pad] + sum_j taps[j] tile[t + j] for the wave's blocks of TT frames; `tile` row i holds source row ta - pad + i.  The
-// window is a ring: tap j = j0 + jj reads elements j ... j + TT - 1, element e sits in slot e % TT, and the slot of element j takes j + TT.
+// out[t] = tile[t + pad] + sum_j taps[j] tile[t + j] for the wave's blocks of TT frames; `tile` row i holds source row ta - pad + i
 __device__ __forceinline__ void filter_tile(float *__restrict__ out, int ldo, const float *__restrict__ tile, const float *__restrict__ taps, int C, int pad,
                                             int ta, int tb, int d, int x, int y) {
   for (int t0 = y * TT; t0 < tb - ta; t0 += kFsmnWaves * TT) {
-    float acc[TT], win[TT];
-#pragma unroll
-    for (int u = 0; u < TT; u++) { acc[u] = 0.0f; win[u] = tile[(t0 + u) * kWave + x]; }
-    // taps and incoming elements of a block of TT taps are read one block AHEAD (16 LDS reads in flight under 64 multiply-adds): with one
-    // wave per SIMD nothing else hides an LDS read that is used the moment it is issued
-    float cn[TT], en[TT];
-#pragma unroll
-    for (int jj = 0; jj < TT; jj++) { cn[jj] = taps[jj * kWave + x]; en[jj] = tile[(t0 + TT + jj) * kWave + x]; }
-    for (int j0 = 0; j0 < C; j0 += TT) {
-      float c[TT], e[TT];
-#pragma unroll
-      for (int jj = 0; jj < TT; jj++) { c[jj] = cn[jj]; e[jj] = en[jj]; }
-      // (reads past tap C - 1 land in the regions' spare rows -- kFsmnSpare of them behind each -- and are never used)
-#pragma unroll
-      for (int jj = 0; jj < TT; jj++) {
-        const int j = j0 + TT + jj;
-        cn[jj] = taps[j * kWave + x];
-        en[jj] = tile[(t0 + TT + j) * kWave + x];
-      }
-      ring_block8(acc, win, c, e, j0, C);
-    }
-#pragma unroll
-    for (int u = 0; u < TT; u++)
-      if (ta + t0 + u < tb) out[(long)(ta + t0 + u) * ldo + d] = tile[(t0 + u + pad) * kWave + x] + acc[u];
+    ring_sweep(taps + x, tile + t0 * kWave + x, C, [=](int u, float a) {
+      if (ta + t0 + u < tb) out[(long)(ta + t0 + u) * ldo + d] = tile[(t0 + u + pad) * kWave + x] + a;
+    });
   }
 }
 
 // out[t] = src[t] + sum_j coef[row(j)] src[t + j - pad] on a tile of 64 columns x kFsmnFrames frames.
-// sm: [kFsmnFrames + C - 1 + kFsmnSpare][64] source rows ta - pad ..., then [C + kFsmnSpare][64] taps in application order.
+// sm: [fsmn_tile_rows(C)][64] source rows ta - pad ..., then [fsmn_tap_rows(C)][64] taps in application order.
 __global__ void __launch_bounds__(kBlock) fsmn_filter_lds(float *__restrict__ out, int ldo, const float *__restrict__ src, int lds_,
                                                           const float *__restrict__ coef, int ldc, int D, int C, int pad, int reverse, int T) {
   extern __shared__ float sm[];
   const int x = threadIdx.x, y = threadIdx.y, d = blockIdx.x * kWave + x;
   const int ta = blockIdx.y * kFsmnFrames, tb = min(T, ta + kFsmnFrames), rows = kFsmnFrames + C - 1;
-  float *tile = sm, *taps = sm + (long)(rows + kFsmnSpare) * kWave;   // (taps: C + kFsmnSpare rows)
+  float *tile = sm, *taps = sm + (long)fsmn_tile_rows(C) * kWave;
   stage_rows_and_taps(tile, src, lds_, ta - pad, rows, TT, T, taps, coef, ldc, C, reverse != 0, d < D, d, x, y);
   __syncthreads();
   if (d < D) filter_tile(out, ldo, tile, taps, C, pad, ta, tb, d, x, y);
 }
 
-constexpr int kFsmnTapsPerThread = 8;   // (= the ring length of ring_block8)
 // Backward of a tile of 64 columns x kFsmnFrames frames [ta, tb):
 //   in_diff[t] = od[t] + sum_j coef[C-1-j] od[t + j - F]                  (cfsmn.h:232-249)
 //   partial[chunk][i] = sum_{t in chunk} in[t + i - P] od[t]               (:213-219)
 // fsmn_grad_finish adds the chunks' partials in a launch of its own, spread over the chip.  (Adding them in the last workgroup of a column
 // tile to arrive, behind a ticket, was measured: the device-scope release in front of the ticket costs every workgroup an L2 write-back --
 // 48 us per launch with every wave fencing, 23 with one thread per workgroup, against 16 + 4.5 for the two launches.)
-// sm: [rows + kFsmnSpare][64] od rows ta - F ..., [rows + kFsmnSpare][64] in rows ta - P ... (rows = kFsmnFrames + C - 1), [C + kFsmnSpare][64] reversed taps.
+// sm: [fsmn_tile_rows(C)][64] od rows ta - F ..., the same of in rows ta - P ..., [fsmn_tap_rows(C)][64] reversed taps.
 __global__ void __launch_bounds__(kBlock) fsmn_backward_fused(float *__restrict__ in_diff, int ldid, float *__restrict__ partial,
                                                               const float *__restrict__ coef, int ldc, const float *__restrict__ in, int ldi,
                                                               const float *__restrict__ od, int ldod, int D, int C, int P, int F, int T) {
   extern __shared__ float sm[];
   const int x = threadIdx.x, y = threadIdx.y, d = blockIdx.x * kWave + x;
   const int chunk = blockIdx.y, ta = chunk * kFsmnFrames, tb = min(T, ta + kFsmnFrames), rows = kFsmnFrames + C - 1;
-  float *odt = sm, *int_ = odt + (long)(rows + kFsmnSpare) * kWave, *taps = int_ + (long)(rows + kFsmnSpare) * kWave;   // (taps: C + kFsmnSpare rows)
+  float *odt = sm, *int_ = odt + (long)fsmn_tile_rows(C) * kWave, *taps = int_ + (long)fsmn_tile_rows(C) * kWave;
   const bool col_ok = d < D;
-  // the in rows are needed behind the in-diff only: their loads (up to 26 per thread; more go the plain way below) leave with the od tile's
-  // and reach LDS when the in-diff is done
+  // the in rows are needed behind the in-diff only: the loads of their first round leave with the od tile's and reach LDS when the in-diff
+  // is done (rows beyond that round follow one at a time)
   float vin[kStageU];
-#pragma unroll
-  for (int u = 0; u < kStageU; u++) {
-    const int i = y + u * kFsmnWaves, r = ta - P + i;
-    vin[u] = (col_ok && i < rows && r >= 0 && r < T) ? in[(unsigned)(r * ldi + d)] : 0.0f;
-  }
+  stage_load(vin, in, ldi, ta - P, rows, T, col_ok, d, y);
   stage_rows_and_taps(odt, od, ldod, ta - F, rows, TT, T, taps, coef, ldc, C, true, col_ok, d, x, y);
   __syncthreads();
   if (col_ok) filter_tile(in_diff, ldid, odt, taps, C, F, ta, tb, d, x, y);
-#pragma unroll
-  for (int u = 0; u < kStageU; u++) {
-    const int i = y + u * kFsmnWaves;
-    if (i < rows) int_[i * kWave + x] = vin[u];
-  }
+  stage_store(int_, vin, rows, x, y);
   for (int i = y + kStageU * kFsmnWaves; i < rows; i += kFsmnWaves) {
-    const int r = ta - P + i;
-    int_[i * kWave + x] = (col_ok && r >= 0 && r < T) ? in[(unsigned)(r * ldi + d)] : 0.0f;
+    float v[1];
+    stage_load(v, in, ldi, ta - P, rows, T, col_ok, d, i);
+    stage_store(int_, v, rows, x, i);
   }
   __syncthreads();
   if (col_ok) {
-    // tap gradients of this chunk: 8 taps per thread, a ring of the in tile sliding down the chunk's frames (frame tt meets in rows
-    // tt + ib ... tt + ib + 7: element e in slot e % 8)
-    constexpr int G = kFsmnTapsPerThread;
-    for (int ib = y * G; ib < C; ib += kFsmnWaves * G) {
-      float acc[G], win[G];
-#pragma unroll
-      for (int j = 0; j < G; j++) { acc[j] = 0.0f; win[j] = int_[(ib + j) * kWave + x]; }
-      const int nt = tb - ta;
-      float gn[G], wn[G];   // read one block of frames ahead, as in filter_tile
-#pragma unroll
-      for (int tj = 0; tj < G; tj++) { gn[tj] = odt[(tj + F) * kWave + x]; wn[tj] = int_[(tj + ib + G) * kWave + x]; }
-      for (int t0 = 0; t0 < nt; t0 += G) {
-        float gs[G], wi[G];
-#pragma unroll
-        for (int tj = 0; tj < G; tj++) { gs[tj] = gn[tj]; wi[tj] = wn[tj]; }
-#pragma unroll
-        for (int tj = 0; tj < G; tj++) {   // (past the chunk: spare rows, never used)
-          const int tt = t0 + G + tj;
-          gn[tj] = odt[(tt + F) * kWave + x];
-          wn[tj] = int_[(tt + ib + G) * kWave + x];
-        }
-        ring_block8(acc, win, gs, wi, t0, nt);
-      }
-#pragma unroll
-      for (int j = 0; j < G; j++)
-        if (ib + j < C) partial[((long)chunk * C + ib + j) * D + d] = acc[j];
+    // tap gradients of this chunk: TT taps per thread, a ring of the in tile sliding down the chunk's frames (frame tt meets in rows
+    // tt + ib ... tt + ib + 7)
+    for (int ib = y * TT; ib < C; ib += kFsmnWaves * TT) {
+      ring_sweep(odt + F * kWave + x, int_ + ib * kWave + x, tb - ta, [=](int j, float a) {
+        if (ib + j < C) partial[((long)chunk * C + ib + j) * D + d] = a;
+      });
     }
   }
 }
@@ -579,16 +561,63 @@ __global__ void __launch_bounds__(kWave * kFsmnFinishTaps) fsmn_grad_finish(floa
 #pragma unroll
     for (int c = 0; c < 32; c++) s += v[c];
   }
-  if (clip > 0.0f) s = fminf(fmaxf(s, -clip), clip);
+  s = clip_to(s, clip);
   corr[(long)i * ldcc + d] = s;
-  if (lr != 0.0f) coef[(long)i * ldc + d] = w_old + -lr * s;
+  if (lr != 0.0f) coef[(long)i * ldc + d] = sgd_step(w_old, lr, s);
 }
 
+// ---- host: launch geometry and dispatch -------------------------------------------------------------------------
+// the plain window kernels: lanes along the columns, TT frames per thread (window_t0), one grid plane per stream
+struct Launch { dim3 grid, block; };
+Launch window_launch(int D, int T, int S = 1) {
+  const int waves = kBlock / kWave;
+  return {dim3((D + kWave - 1) / kWave, (T + TT * waves - 1) / (TT * waves), S), dim3(kWave, waves)};
+}
 // rows per chunk so that (column tiles x chunks) is a few hundred blocks
 int rows_per_chunk(int rows, int ctiles) {
   int want = (512 + ctiles - 1) / ctiles;
   int rpc = (rows + want - 1) / want;
   return rpc < 16 ? 16 : rpc;
+}
+
+// LDS budget of the tiled CompactFsmn kernels (of the CU's 160 KB), in rows of 64 floats; a kernel is allowed it once, before its first launch
+constexpr int kFsmnLdsRows = 512;   // 128 KB
+size_t lds_bytes(int rows) { return sizeof(float) * (size_t)rows * kWave; }
+template <auto KERNEL>
+void allow_lds_budget() {
+  static const bool once = [] {
+    ASLP_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes(kFsmnLdsRows)));
+    return true;
+  }();
+  (void)once;
+}
+
+// ring length of the streaming RowConvolution kernels at K + 1 taps (the instantiation <ring, ring == K + 1 && ring == 21>); 0: more taps
+// than they serve
+int rowconv_ring(int K) {
+  return K + 1 == 21 ? 21   // FutureContext 20 (the recipes' value): no tap is tested
+         : K + 1 <= 4 ? 4 : K + 1 <= 8 ? 8 : K + 1 <= 16 ? 16 : K + 1 <= 32 ? 32 : 0;
+}
+// f(KP, EXACT) as integral constants for the ring that serves K (the caller has checked that one does): with rowconv_ring the only list of
+// the streaming kernels' instantiations
+template <typename F>
+void with_ring(int K, F &&f) {
+  switch (rowconv_ring(K)) {
+    case 21: f(std::integral_constant<int, 21>{}, std::true_type{}); break;
+    case 4: f(std::integral_constant<int, 4>{}, std::false_type{}); break;
+    case 8: f(std::integral_constant<int, 8>{}, std::false_type{}); break;
+    case 16: f(std::integral_constant<int, 16>{}, std::false_type{}); break;
+    default: f(std::integral_constant<int, 32>{}, std::false_type{});
+  }
+}
+// grid of the streaming kernels over `rows` rows of time, which rc_place reads back: strips of kRcCols columns x kRcStreams streams, padded to
+// a multiple of the 8 XCDs, times chunks of kRcChunk rows
+constexpr int kRcChunk = 64;   // frames per chunk: the K halo rows cost (64 + K) / 64 of the reads
+struct RcGrid { int dtiles, sgroups, nstrips, tc, nchunks; dim3 grid, block; };
+RcGrid rc_grid(int D, int S, int rows) {
+  const int dtiles = (D + kRcCols - 1) / kRcCols, sgroups = (S + kRcStreams - 1) / kRcStreams, nstrips = dtiles * sgroups;
+  const int nchunks = (rows + kRcChunk - 1) / kRcChunk;
+  return {dtiles, sgroups, nstrips, kRcChunk, nchunks, dim3(8 * ((nstrips + 7) / 8) * nchunks), dim3(kWave, kRcStreams)};
 }
 
 }  // namespace
@@ -598,12 +627,10 @@ using namespace aslp;
 
 extern "C" {
 
-// LDS budget of the tiled CompactFsmn kernels (of the CU's 160 KB): rows of 64 floats
-static constexpr int kFsmnLdsRows = 512;   // 128 KB
 static bool fsmn_fits32(long rows, long ld) { return rows * ld < (1L << 30); }   // element offsets of the tiled kernels are 32-bit
 // LDS rows of the tiled forward (source rows + taps) and of the fused backward (od rows + in rows + taps) at C taps
-static int fsmn_forward_lds_rows(int C) { return kFsmnFrames + C - 1 + kFsmnSpare + C + kFsmnSpare; }
-static int fsmn_backward_lds_rows(int C) { return 2 * (kFsmnFrames + C - 1 + kFsmnSpare) + C + kFsmnSpare; }
+static int fsmn_forward_lds_rows(int C) { return fsmn_tile_rows(C) + fsmn_tap_rows(C); }
+static int fsmn_backward_lds_rows(int C) { return 2 * fsmn_tile_rows(C) + fsmn_tap_rows(C); }
 // the tiled forward serves C <= 216 taps, the fused backward C <= 126; both need 32-bit element offsets
 static bool fsmn_forward_tiled(int C, int T, int ldo, int lds, int ldc) {
   return fsmn_forward_lds_rows(C) <= kFsmnLdsRows && fsmn_fits32(T, lds) && fsmn_fits32(T, ldo) && fsmn_fits32(C, ldc);
@@ -625,17 +652,12 @@ void aslp_fsmn_filter(float *out, int ldo, const float *src, int lds, const floa
   if (T <= 0 || D <= 0) return;
   const int C = past + future + 1, pad = reverse ? future : past;
   if (fsmn_forward_tiled(C, T, ldo, lds, ldc)) {
-    const size_t lds_bytes = sizeof(float) * (size_t)fsmn_forward_lds_rows(C) * kWave;
-    static bool attr_set = false;
-    if (!attr_set) {
-      ASLP_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(fsmn_filter_lds), hipFuncAttributeMaxDynamicSharedMemorySize, kFsmnLdsRows * kWave * sizeof(float)));
-      attr_set = true;
-    }
-    hipLaunchKernelGGL(fsmn_filter_lds, dim3((D + kWave - 1) / kWave, (T + kFsmnFrames - 1) / kFsmnFrames), dim3(kWave, kFsmnWaves), lds_bytes, cur_stream(), out, ldo,
-                       src, lds, coef, ldc, D, C, pad, reverse, T);
+    allow_lds_budget<fsmn_filter_lds>();
+    hipLaunchKernelGGL(fsmn_filter_lds, dim3((D + kWave - 1) / kWave, (T + kFsmnFrames - 1) / kFsmnFrames), dim3(kWave, kFsmnWaves),
+                       lds_bytes(fsmn_forward_lds_rows(C)), cur_stream(), out, ldo, src, lds, coef, ldc, D, C, pad, reverse, T);
   } else {   // a filter too long for the tile
-    dim3 block(kWave, kBlock / kWave), grid((D + kWave - 1) / kWave, (T + TT * (kBlock / kWave) - 1) / (TT * (kBlock / kWave)));
-    hipLaunchKernelGGL(fsmn_filter, grid, block, 0, cur_stream(), out, ldo, src, lds, coef, ldc, D, C, pad, reverse, T);
+    const Launch l = window_launch(D, T);
+    hipLaunchKernelGGL(fsmn_filter, l.grid, l.block, 0, cur_stream(), out, ldo, src, lds, coef, ldc, D, C, pad, reverse, T);
   }
   check_launch("aslp_fsmn_filter");
 }
@@ -643,9 +665,7 @@ void aslp_fsmn_filter(float *out, int ldo, const float *src, int lds, const floa
 void aslp_fsmn_backward(float *in_diff, int ldid, float *coef_corr, int ldcc, float *coef, int ldc, const float *in, int ldi, const float *out_diff,
                         int ldod, int D, int past, int future, int T, float clip, float lr) {
   if (T <= 0 || D <= 0) return;
-  const int C = past + future + 1, ctiles = (D + kWave - 1) / kWave;
-  const int nchunks = (T + kFsmnFrames - 1) / kFsmnFrames;
-  const int lds_rows = fsmn_backward_lds_rows(C);
+  const int C = past + future + 1, ctiles = (D + kWave - 1) / kWave, nchunks = (T + kFsmnFrames - 1) / kFsmnFrames;
   if (!fsmn_backward_is_fused(D, C, T, ldid, ldc, ldi, ldod)) {   // a filter too long for the tile (or offsets beyond 32 bits): the separate kernels
     aslp_fsmn_coef_grad(coef_corr, ldcc, in, ldi, out_diff, ldod, D, past, future, T, clip);
     aslp_fsmn_filter(in_diff, ldid, out_diff, ldod, coef, ldc, D, past, future, T, 1);
@@ -657,12 +677,8 @@ void aslp_fsmn_backward(float *in_diff, int ldid, float *coef_corr, int ldcc, fl
   }
   float *partial = static_cast<float *>(scratch(kScratchMisc, sizeof(float) * (size_t)nchunks * C * D));
   if (!partial) { set_error("aslp_fsmn_backward: no scratch for the tap-gradient partials -- nothing was launched (no in_diff, no gradient, no step)"); return; }
-  static bool attr_set = false;
-  if (!attr_set) {
-    ASLP_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(fsmn_backward_fused), hipFuncAttributeMaxDynamicSharedMemorySize, kFsmnLdsRows * kWave * sizeof(float)));
-    attr_set = true;
-  }
-  hipLaunchKernelGGL(fsmn_backward_fused, dim3(ctiles, nchunks), dim3(kWave, kFsmnWaves), sizeof(float) * (size_t)lds_rows * kWave, cur_stream(), in_diff, ldid,
+  allow_lds_budget<fsmn_backward_fused>();
+  hipLaunchKernelGGL(fsmn_backward_fused, dim3(ctiles, nchunks), dim3(kWave, kFsmnWaves), lds_bytes(fsmn_backward_lds_rows(C)), cur_stream(), in_diff, ldid,
                      partial, coef, ldc, in, ldi, out_diff, ldod, D, C, past, future, T);
   hipLaunchKernelGGL(fsmn_grad_finish, dim3(ctiles, (C + kFsmnFinishTaps - 1) / kFsmnFinishTaps), dim3(kWave, kFsmnFinishTaps), 0, cur_stream(), coef_corr, ldcc,
                      coef, ldc, partial, D, C, nchunks, clip, lr);
@@ -675,7 +691,7 @@ void aslp_fsmn_coef_grad(float *coef_corr, int ldc, const float *in, int ldi, co
   const int C = past + future + 1, ctiles = (D + kWave - 1) / kWave;
   const int rpc = rows_per_chunk(T, ctiles), chunks = (T + rpc - 1) / rpc;
   float *partial = static_cast<float *>(scratch(kScratchMisc, sizeof(float) * (size_t)chunks * C * D));
-  if (!partial) return;
+  if (!partial) { set_error("aslp_fsmn_coef_grad: no scratch for the tap-gradient partials -- nothing was launched (no gradient)"); return; }
   hipLaunchKernelGGL(fsmn_coef_grad1, dim3(ctiles, chunks), dim3(kWave, kBlock / kWave), 0, cur_stream(), partial, in, ldi, out_diff, ldod,
                      D, C, past, T, rpc);
   hipLaunchKernelGGL(fsmn_coef_grad2, dim3(grid_for((long)C * D)), dim3(kBlock), 0, cur_stream(), coef_corr, ldc, partial, D, C, chunks,
@@ -684,11 +700,6 @@ void aslp_fsmn_coef_grad(float *coef_corr, int ldc, const float *in, int ldi, co
 }
 
 // the streaming RowConvolution kernels serve up to 32 taps on even widths with 8-byte aligned rows
-// ring length of the streaming kernels at K + 1 taps (the instantiation <ring, ring == K + 1 && ring == 21>); 0: more taps than they serve
-static int rowconv_ring(int K) {
-  return K + 1 == 21 ? 21   // FutureContext 20 (the recipes' value): no tap is tested
-         : K + 1 <= 4 ? 4 : K + 1 <= 8 ? 8 : K + 1 <= 16 ? 16 : K + 1 <= 32 ? 32 : 0;
-}
 // (the forward has two matrices: ld_c = 0, c = nullptr)
 static bool rowconv_stream_serves(int D, int K, int ld_a, int ld_b, int ld_c, const void *a, const void *b, const void *c) {
   return rowconv_ring(K) != 0 && !(D & 1) && !(ld_a & 1) && !(ld_b & 1) && !(ld_c & 1) && !(reinterpret_cast<uintptr_t>(a) & 7u) &&
@@ -699,29 +710,20 @@ static bool rowconv_stream_serves(int D, int K, int ld_a, int ld_b, int ld_c, co
 int aslp_rowconv_path(int D, int K, int ld_a, int ld_b, int ld_c, const void *a, const void *b, const void *c) {
   return rowconv_stream_serves(D, K, ld_a, ld_b, ld_c, a, b, c) ? rowconv_ring(K) : 0;
 }
-static constexpr int kRcChunk = 64;   // frames per chunk: the K halo rows cost (64 + K) / 64 of the reads
 
 void aslp_rowconv_forward(float *out, int ldo, const float *in, int ldi, const float *w, int D, int K, int T, int S,
                           const int32_cuda *seq_len) {
   if (T <= 0 || D <= 0 || S <= 0) return;
   if (rowconv_stream_serves(D, K, ldo, ldi, 0, out, in, nullptr)) {
-    const int dtiles = (D + kRcCols - 1) / kRcCols, sgroups = (S + kRcStreams - 1) / kRcStreams, nstrips = dtiles * sgroups;
-    const int tc = kRcChunk, nchunks = (T + tc - 1) / tc;
-    const dim3 grid(8 * ((nstrips + 7) / 8) * nchunks), block(kWave, kRcStreams);
-#define ASLP_RC_FWD(KP, EXACT) hipLaunchKernelGGL((rowconv_fwd_stream<KP, EXACT>), grid, block, 0, cur_stream(), out, ldo, in, ldi, w, D, K, T, S, seq_len, tc, nchunks, dtiles, nstrips)
-    switch (rowconv_ring(K)) {
-      case 21: ASLP_RC_FWD(21, true); break;
-      case 4: ASLP_RC_FWD(4, false); break;
-      case 8: ASLP_RC_FWD(8, false); break;
-      case 16: ASLP_RC_FWD(16, false); break;
-      default: ASLP_RC_FWD(32, false);
-    }
-#undef ASLP_RC_FWD
-    check_launch("aslp_rowconv_forward");
-    return;
+    const RcGrid g = rc_grid(D, S, T);
+    with_ring(K, [&](auto KP, auto EXACT) {
+      hipLaunchKernelGGL((rowconv_fwd_stream<decltype(KP)::value, decltype(EXACT)::value>), g.grid, g.block, 0, cur_stream(), out, ldo, in, ldi, w, D, K, T, S,
+                         seq_len, g.tc, g.nchunks, g.dtiles, g.nstrips);
+    });
+  } else {
+    const Launch l = window_launch(D, T, S);
+    hipLaunchKernelGGL(rowconv_fwd, l.grid, l.block, 0, cur_stream(), out, ldo, in, ldi, w, D, K, T, S, seq_len);
   }
-  dim3 block(kWave, kBlock / kWave), grid((D + kWave - 1) / kWave, (T + TT * (kBlock / kWave) - 1) / (TT * (kBlock / kWave)), S);
-  hipLaunchKernelGGL(rowconv_fwd, grid, block, 0, cur_stream(), out, ldo, in, ldi, w, D, K, T, S, seq_len);
   check_launch("aslp_rowconv_forward");
 }
 
@@ -740,20 +742,14 @@ void aslp_rowconv_backward_fused(float *in_diff, int ldid, float *w_diff, const 
     }
     return;
   }
-  const int dtiles = (D + kRcCols - 1) / kRcCols, sgroups = (S + kRcStreams - 1) / kRcStreams, nstrips = dtiles * sgroups;
-  const int tc = kRcChunk, nchunks = (T + K + tc - 1) / tc, nparts = nchunks * sgroups;
+  const RcGrid g = rc_grid(D, S, T + K);   // (the rows of the out-diff ring: the last K meet the tail of the taps only)
+  const int nparts = g.nchunks * g.sgroups;
   float *partial = static_cast<float *>(scratch(kScratchMisc, sizeof(float) * (size_t)nparts * (K + 1) * D));
   if (!partial) { set_error("aslp_rowconv_backward_fused: no scratch for the tap-gradient partials -- nothing was launched (no in_diff, no gradient, no step)"); return; }
-  const dim3 grid(8 * ((nstrips + 7) / 8) * nchunks), block(kWave, kRcStreams);
-#define ASLP_RC_BWD(KP, EXACT) hipLaunchKernelGGL((rowconv_bwd_fused<KP, EXACT>), grid, block, 0, cur_stream(), in_diff, ldid, partial, in, ldi, out_diff, ldod, w, D, K, T, S, seq_len, tc, nchunks, dtiles, nstrips, sgroups)
-  switch (rowconv_ring(K)) {
-    case 21: ASLP_RC_BWD(21, true); break;
-    case 4: ASLP_RC_BWD(4, false); break;
-    case 8: ASLP_RC_BWD(8, false); break;
-    case 16: ASLP_RC_BWD(16, false); break;
-    default: ASLP_RC_BWD(32, false);
-  }
-#undef ASLP_RC_BWD
+  with_ring(K, [&](auto KP, auto EXACT) {
+    hipLaunchKernelGGL((rowconv_bwd_fused<decltype(KP)::value, decltype(EXACT)::value>), g.grid, g.block, 0, cur_stream(), in_diff, ldid, partial, in, ldi, out_diff,
+                       ldod, w, D, K, T, S, seq_len, g.tc, g.nchunks, g.dtiles, g.nstrips, g.sgroups);
+  });
   hipLaunchKernelGGL(rowconv_wgrad_finish, dim3((D + kWave - 1) / kWave, K + 1), dim3(kWave, kFinishWaves), 0, cur_stream(), w_diff, partial, D, K, nparts,
                      w_corr, w, momentum, learn_rate, update);
   check_launch("aslp_rowconv_backward_fused");
@@ -762,8 +758,8 @@ void aslp_rowconv_backward_fused(float *in_diff, int ldid, float *w_diff, const 
 void aslp_rowconv_backward(float *in_diff, int ldid, const float *out_diff, int ldod, const float *w, int D, int K, int T, int S,
                            const int32_cuda *seq_len) {
   if (T <= 0 || D <= 0 || S <= 0) return;
-  dim3 block(kWave, kBlock / kWave), grid((D + kWave - 1) / kWave, (T + TT * (kBlock / kWave) - 1) / (TT * (kBlock / kWave)), S);
-  hipLaunchKernelGGL(rowconv_bwd, grid, block, 0, cur_stream(), in_diff, ldid, out_diff, ldod, w, D, K, T, S, seq_len);
+  const Launch l = window_launch(D, T, S);
+  hipLaunchKernelGGL(rowconv_bwd, l.grid, l.block, 0, cur_stream(), in_diff, ldid, out_diff, ldod, w, D, K, T, S, seq_len);
   check_launch("aslp_rowconv_backward");
 }
 
@@ -780,7 +776,7 @@ void aslp_rowconv_wgrad(float *w_diff, const float *in, int ldi, const float *ou
   const int spg = (S + sg - 1) / sg;
   sg = (S + spg - 1) / spg;
   float *partial = static_cast<float *>(scratch(kScratchMisc, sizeof(float) * (size_t)chunks * sg * (K + 1) * D));
-  if (!partial) return;
+  if (!partial) { set_error("aslp_rowconv_wgrad: no scratch for the tap-gradient partials -- nothing was launched (no gradient)"); return; }
   dim3 grid(ctiles, chunks, sg), block(kWave, waves);
   if (K + 1 <= 8) hipLaunchKernelGGL((rowconv_wgrad1<8>), grid, block, 0, cur_stream(), partial, in, ldi, out_diff, ldod, D, K, T, S, seq_len, tc, spg, 0);
   else if (K + 1 <= 16) hipLaunchKernelGGL((rowconv_wgrad1<16>), grid, block, 0, cur_stream(), partial, in, ldi, out_diff, ldod, D, K, T, S, seq_len, tc, spg, 0);
