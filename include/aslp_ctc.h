@@ -16,6 +16,8 @@
 #ifndef ASLP_CTC_H_
 #define ASLP_CTC_H_
 #include <stddef.h>
+
+#include "aslp_matrixdim.h"
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -70,6 +72,25 @@ ctcStatus_t aslp_ctc_loss_strided(const float *acts, int ld_acts, float *grads, 
  * pzx_host[n] = log p(z|x) (-1e30 = the reference's log_zero_ when there is no alignment). */
 ctcStatus_t aslp_eesen_ctc_mseq(const float *net_out, int ld, float *diff, int ld_diff, const int *flat_labels, const int *label_lengths,
                                 const int *frame_num, int alphabet_size, int minibatch, float *pzx_host);
+
+/* CTC token errors on the device (WarpCtc::ErrorRate warp-ctc.cc:487-529, Ctc::ErrorRate / ErrorRateMSeq ctc-loss.cc:346-424): per
+ * utterance the best path -- argmax id per frame (first strict maximum, as aslp_find_row_max_id), repeats collapsed, blanks (0) dropped --
+ * and its unit-cost Levenshtein distance to the reference labels.  One workgroup per utterance; hypotheses of any length, reference
+ * label sequences of up to 1024 tokens: aslp_ctc_token_errors_supported() says whether a batch with these maxima is served.  A batch
+ * that is not, or every batch under aslp_ctc_errors_on_host(1) / ASLP_CTC_ERRORS_HOST=1 (read once per process; on < 0 gives the
+ * decision back to the environment), takes the host path, whole: argmax launch, blocking copy of the ids, host loop.
+ * aslp_ctc_errors_last_path(): which path the last call took (this one, or an ErrorRate* of the loss classes): 0 host, 1 device.
+ *
+ * aslp_ctc_token_errors is the synchronous form: net_out on the device, utterance s of num_seq owns rows f * num_seq + s, f < frames[s];
+ * frames == NULL means one sequence of d.rows frames.  errors[s], hyp_lens[s] and (hyps != NULL) the first min(hyp_lens[s], hyp_ld)
+ * tokens of hypothesis s at hyps + s * hyp_ld are written on the host.  Returns 0, 1 = bad arguments, 2 = a runtime failure
+ * (aslp_get_last_error()).  Runs on the aslp_set_stream() stream. */
+int aslp_ctc_token_errors_supported(int max_frames, int max_label_len);
+int aslp_ctc_token_errors(const float *net_out, MatrixDim d, const int *frames, int num_seq, const int *flat_labels,
+                          const int *label_lengths, int *errors, int *hyp_lens, int *hyps, int hyp_ld);
+void aslp_ctc_errors_on_host(int on);
+int aslp_ctc_errors_on_host_get(void);
+int aslp_ctc_errors_last_path(void);
 
 #ifdef __cplusplus
 }

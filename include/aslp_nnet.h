@@ -98,7 +98,10 @@ void aslp_warpctc_free(aslp_warpctc_t w);
  * filtered, +-1-clipped gradient; costs_host[num_utt] (may be NULL) the per-utterance -log p(l|x). */
 int aslp_warpctc_eval(aslp_warpctc_t w, const int32_t *frame_num_utt, int num_utt, const float *net_out, int rows, int cols, int stride,
                       const int32_t *flat_labels, const int32_t *label_lengths, float *diff, int diff_stride, float *costs_host);
-/* WarpCtc::ErrorRate (warp-ctc.cc:487): best-path token errors vs the labels, accumulated into the report */
+/* WarpCtc::ErrorRate (warp-ctc.cc:487): best-path token errors vs the labels, accumulated into the report.  Counted on the device
+ * (aslp_ctc.h: aslp_ctc_token_errors*): the call queues the work on the launch stream and returns; net_out is read there, in stream
+ * order, so whatever overwrites or frees it must be ordered behind this call on that stream (as everything of this library is);
+ * report / get_stats / the next eval book the counts first.  The same holds for aslp_eesenctc_error_rate with frame_num_utt. */
 int aslp_warpctc_error_rate(aslp_warpctc_t w, const int32_t *frame_num_utt, int num_utt, const float *net_out, int rows, int cols, int stride,
                             const int32_t *flat_labels, const int32_t *label_lengths);
 int aslp_warpctc_report(aslp_warpctc_t w, char *buf, int buflen);   /* WarpCtc::Report warp-ctc.cc:531 */

@@ -278,6 +278,12 @@ _sig("compute_ctc_loss", _i, _vp, _vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C
 _sig("get_workspace_size", _i, C.POINTER(C.c_int), C.POINTER(C.c_int), _i, _i, CtcComputeInfo, C.POINTER(C.c_size_t))
 _sig("ctcGetStatusString", C.c_char_p, _i)
 _sig("get_warpctc_version", _i)
+_ip = C.POINTER(C.c_int)
+_sig("aslp_ctc_token_errors_supported", _i, _i, _i)
+_sig("aslp_ctc_token_errors", _i, _vp, _md, _ip, _i, _ip, _ip, _ip, _ip, _ip, _i)
+_sig("aslp_ctc_errors_on_host", None, _i)
+_sig("aslp_ctc_errors_on_host_get", _i)
+_sig("aslp_ctc_errors_last_path", _i)
 
 
 def check_error():

@@ -37,6 +37,7 @@ void RunLattice(const CuMatrixBase &net_out, const std::vector<int32> &frame_num
 }  // namespace
 
 void Ctc::Eval(const CuMatrixBase &net_out, const std::vector<int32> &label, CuMatrix *diff) {  // ctc-loss.cc:31-109
+  token_errors_.Settle(&book_);  // the batch before is booked ahead of this one's progress line
   std::vector<int32> frames(1, net_out.NumRows());
   std::vector<std::vector<int32>> labels(1, label);
   RunLattice(net_out, frames, labels, diff, &last_costs_);
@@ -51,6 +52,7 @@ void Ctc::Eval(const CuMatrixBase &net_out, const std::vector<int32> &label, CuM
 
 void Ctc::EvalParallel(const std::vector<std::string> &utt, const std::vector<int32> &frame_num_utt, const CuMatrixBase &net_out,
                        std::vector<std::vector<int32>> &label, CuMatrix *diff) {  // ctc-loss.cc:115-227
+  token_errors_.Settle(&book_);  // the batch before is booked ahead of this one's progress line
   RunLattice(net_out, frame_num_utt, label, diff, &last_costs_);
 #if CTC_GRAD_CHECK == SUM_LOSS_CHECK
   StatAndLossCheck(utt, frame_num_utt, last_costs_, diff);
@@ -76,6 +78,19 @@ static void BestPath(const std::vector<int32> &ids, int first, int step, int fra
 }
 
 void Ctc::ErrorRate(const CuMatrixBase &net_out, const std::vector<int32> &label, float *err_rate, std::vector<int32> *hyp) {  // :346-383
+  token_errors_.Settle(&book_);
+  const int32 frames = net_out.NumRows();
+  if (!ctc_errors_host_path() && frames > 0 && aslp_ctc_token_errors_supported(frames, label.size())) {
+    int errs = 0, hyp_len = 0, ref_len = label.size();
+    hyp->resize(frames);
+    if (aslp_ctc_token_errors(net_out.Data(), net_out.Dim(), NULL, 1, label.data(), &ref_len, &errs, &hyp_len, hyp->data(), frames) != 0)
+      ASLP_ERR << "Ctc::ErrorRate: the token errors could not be computed";
+    hyp->resize(hyp_len);
+    book_.CountTokens(errs, label.size());
+    *err_rate = (100.0 * errs) / label.size();
+    return;
+  }
+  ctc_errors_note_path(0);
   CuArray<int32> maxid;
   net_out.FindRowMaxId(&maxid);
   std::vector<int32> data;
@@ -88,6 +103,9 @@ void Ctc::ErrorRate(const CuMatrixBase &net_out, const std::vector<int32> &label
 }
 
 void Ctc::ErrorRateMSeq(const std::vector<int> &frame_num_utt, const CuMatrixBase &net_out, std::vector<std::vector<int>> &label) {  // :385-424
+  token_errors_.Settle(&book_);
+  if (token_errors_.Enqueue(frame_num_utt, net_out, label)) return;
+  ctc_errors_note_path(0);
   CuArray<int32> maxid;
   net_out.FindRowMaxId(&maxid);
   std::vector<int32> data;

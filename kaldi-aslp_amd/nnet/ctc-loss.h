@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "ctc-cost-book.h"
+#include "ctc-token-errors.h"
 #include "cu-matrix.h"
 
 namespace aslp {
@@ -23,12 +24,15 @@ class Ctc {
   void Eval(const CuMatrixBase &net_out, const std::vector<int32> &label, CuMatrix *diff);
   void EvalParallel(const std::vector<std::string> &utt, const std::vector<int32> &frame_num_utt, const CuMatrixBase &net_out,
                     std::vector<std::vector<int32>> &label, CuMatrix *diff);
+  // Token errors of the best paths against the labels, counted on the device (ctc-token-errors.h).  ErrorRate hands err and hyp back, so
+  // it waits for them; ErrorRateMSeq returns without waiting and whatever reads the token totals settles first.
+  // aslp_ctc_errors_on_host(1) / ASLP_CTC_ERRORS_HOST=1, or a batch the kernel does not serve, takes the host loop.
   void ErrorRate(const CuMatrixBase &net_out, const std::vector<int32> &label, float *err, std::vector<int32> *hyp);
   void ErrorRateMSeq(const std::vector<int> &frame_num_utt, const CuMatrixBase &net_out, std::vector<std::vector<int>> &label);
   void SetReportStep(int32 report_step) { book_.SetReportStep(report_step); }
-  std::string Report() { return book_.Report(); }
-  float NumErrorTokens() const { return book_.NumErrorTokens(); }
-  int32 NumRefTokens() const { return book_.NumRefTokens(); }
+  std::string Report() { token_errors_.Settle(&book_); return book_.Report(); }
+  float NumErrorTokens() { token_errors_.Settle(&book_); return book_.NumErrorTokens(); }
+  int32 NumRefTokens() { token_errors_.Settle(&book_); return book_.NumRefTokens(); }
   // the reference's three bookkeeping variants (ctc-loss.cc:229-302, 304-329, 331-344), over the shared book
   void StatOnly(const std::vector<std::string> &, const std::vector<int32> &frame_num_utt, const std::vector<float> &pzx_host, CuMatrix *) {
     book_.AcceptAll(frame_num_utt, pzx_host);
@@ -48,6 +52,7 @@ class Ctc {
 
  private:
   CtcCostBook book_;   // window of 100 utterances (ctc-loss.cc: stat_period_)
+  DeferredTokenErrors token_errors_;   // the last ErrorRateMSeq batch while its counts are on their way
   std::vector<float> last_costs_;
 };
 

@@ -14,6 +14,7 @@ WarpCtc::WarpCtc() : use_gpu_(true), book_(500) {}
 void WarpCtc::Eval(const std::vector<std::string> &utt, const std::vector<int32> &frame_num_utt, const CuMatrixBase &net_out,
                    const std::vector<std::vector<int32>> &labels, CuMatrix *diff) {  // warp-ctc.cc:33-46
   ASLP_ASSERT(diff != NULL);
+  token_errors_.Settle(&book_);  // the batch before is booked ahead of this one's progress line
   if (use_gpu_) EvalGpu(utt, frame_num_utt, net_out, labels, diff);
   else EvalCpu(utt, frame_num_utt, net_out, labels, diff);
 }
@@ -67,6 +68,9 @@ void WarpCtc::EvalGpu(const std::vector<std::string> &utt, const std::vector<int
 }
 
 void WarpCtc::ErrorRate(const std::vector<int> &frame_num_utt, const CuMatrixBase &net_out, std::vector<std::vector<int>> &label) {  // :487-529
+  token_errors_.Settle(&book_);
+  if (token_errors_.Enqueue(frame_num_utt, net_out, label)) return;
+  ctc_errors_note_path(0);
   CuArray<int32> maxid;
   net_out.FindRowMaxId(&maxid);
   std::vector<int32> data;

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "ctc-cost-book.h"
+#include "ctc-token-errors.h"
 #include "cu-matrix.h"
 
 namespace aslp {
@@ -29,11 +30,14 @@ class WarpCtc {
   // No host fallback exists in this library: fails loudly (the reference's EvalCpu ran cpu_ctc.h on the host)
   void EvalCpu(const std::vector<std::string> &utt, const std::vector<int32> &frame_num_utt, const CuMatrixBase &net_out,
                const std::vector<std::vector<int32>> &labels, CuMatrix *diff);
+  // Token errors of the batch's best paths against the labels.  Counted on the device behind the loss and booked later (ctc-token-errors.h):
+  // the call returns without waiting; whatever reads the token totals settles first.  aslp_ctc_errors_on_host(1) /
+  // ASLP_CTC_ERRORS_HOST=1, or a batch the kernel does not serve, takes the host loop.
   void ErrorRate(const std::vector<int> &frame_num_utt, const CuMatrixBase &net_out, std::vector<std::vector<int>> &label);
   void SetReportStep(int32 report_step) { book_.SetReportStep(report_step); }
-  std::string Report() { return book_.Report(); }
-  float NumErrorTokens() const { return book_.NumErrorTokens(); }
-  int32 NumRefTokens() const { return book_.NumRefTokens(); }
+  std::string Report() { token_errors_.Settle(&book_); return book_.Report(); }
+  float NumErrorTokens() { token_errors_.Settle(&book_); return book_.NumErrorTokens(); }
+  int32 NumRefTokens() { token_errors_.Settle(&book_); return book_.NumRefTokens(); }
   void SetUseGpu(bool use_gpu) { use_gpu_ = use_gpu; }
   // the reference's three bookkeeping variants (warp-ctc.cc:288-365, 446-470, 472-485), over the shared book
   void StatOnly(const std::vector<std::string> &, const std::vector<int32> &frame_num_utt, const std::vector<float> &pzx_host, CuMatrix *) {
@@ -56,6 +60,7 @@ class WarpCtc {
  private:
   bool use_gpu_;
   CtcCostBook book_;   // window of 500 utterances (warp-ctc.cc: stat_period_)
+  DeferredTokenErrors token_errors_;   // the last ErrorRate batch while its counts are on their way
   std::vector<float> last_costs_;
 };
 

@@ -342,6 +342,36 @@ def ctc_loss(acts, labels, input_lengths, want_grad=True):
     return np.array(list(costs), np.float32), grads
 
 
+def ctc_token_errors(acts, labels, input_lengths=None):
+    """aslp_ctc_token_errors (include/aslp_ctc.h) on device activations [(maxT*mb) x A], row t * mb + n: per utterance the best path
+    (argmax, first strict maximum; repeats collapsed; blanks dropped) and its edit distance to the labels.
+    labels: list of int lists; input_lengths None: one sequence of all rows.  Returns (errors numpy[mb] int32, hyps list of int lists)."""
+    import numpy as np
+    _chk(acts)
+    mb = len(labels)
+    flat = [int(v) for l in labels for v in l] or [0]
+    flat_c = (C.c_int * len(flat))(*flat)
+    lab_len = (C.c_int * mb)(*[len(l) for l in labels])
+    in_len = None if input_lengths is None else (C.c_int * mb)(*[int(t) for t in input_lengths])
+    hyp_ld = max(1, acts.shape[0] if input_lengths is None else max(int(t) for t in input_lengths))
+    errors = np.zeros(mb, np.int32)
+    hyp_lens = np.zeros(mb, np.int32)
+    hyps = np.zeros((mb, hyp_ld), np.int32)
+    ip = C.POINTER(C.c_int)
+    rc = lib.aslp_ctc_token_errors(ptr(acts), dim(acts), in_len, mb, flat_c, lab_len, errors.ctypes.data_as(ip), hyp_lens.ctypes.data_as(ip),
+                                   hyps.ctypes.data_as(ip), hyp_ld)
+    check_error()
+    if rc != 0:
+        raise ValueError("aslp_ctc_token_errors argument error %d" % rc)
+    return errors, [hyps[n, :hyp_lens[n]].tolist() for n in range(mb)]
+
+
+def ctc_errors_on_host(n):
+    """1: the token errors of the CTC losses (and of ctc_token_errors) take the host loop; 0: the device kernel wherever it serves the batch;
+    -1: what ASLP_CTC_ERRORS_HOST said"""
+    lib.aslp_ctc_errors_on_host(int(n))
+
+
 # ---- depthwise temporal filters (csrc/temporal.hip; nnet-cfsmn-component.h:170-262, nnet-row-convolution.cc:105-186) ----
 def fsmn_forward(out, x, coef, past, future):
     """out[t] = x[t] + sum_j coef[j] .* x[t + j - past]; coef [(past + future + 1) x D]"""
