@@ -1,5 +1,5 @@
 """Times aslp_sgemm on the BASELINE cfg shapes (HIP events on torch's stream).
-TILES=0,3,4 python devtools/bench_gemm.py  sweeps forced tile configs (0 = heuristic)."""
+TILES=0,7,12 python devtools/bench_gemm.py  sweeps forced tile configs (0 = heuristic; register-staged 1, 7, 12; LDS-DMA 205..208, 211..213)."""
 import os, sys, torch
 sys.path.insert(0, '.')
 import aslp_import; aslp = aslp_import.load(); aslp.ops.use_torch_stream()

@@ -302,7 +302,9 @@ int aslp_sgemm_pair_ex(int transA, int transB, int M, int N, int K, float alpha,
  * profiling was enabled with aslp_gemm_profile(1)) event-timed milliseconds. */
 void aslp_gemm_profile(int enable);
 void aslp_gemm_profile_reset(void);
-/* tuning aid: force tile config 1..5 (0 = heuristic).  1: 32x128x16  2: 64x64x16  3: 128x64x32  4: 128x128x32  5: 128x128x16 */
+/* tuning aid: force a tile configuration of the fp32 product kernels (0 = heuristic), by the numbers aslp_gemm_profile_tile names.
+ * Register-staged: 1 (32x128x16), 7 (64x64x32), 12 (64x128x32, 8 waves).  LDS-DMA: 205..208, 211..213, which fall back to 1 / 7 / 12
+ * where they are not eligible.  Any other number makes the next product report "unknown tile configuration". */
 void aslp_gemm_force_tile(int cfg);
 /* tile configuration of the calling thread's latest aslp_sgemm / aslp_sgemm_ex (the numbers aslp_gemm_profile_tile names) */
 int aslp_gemm_last_tile(void);

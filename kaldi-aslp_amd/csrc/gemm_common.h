@@ -230,6 +230,17 @@ __host__ __device__ __forceinline__ bool gemm_epilogue_wide_ok(const GemmArgs &g
          (!ep.c_src || ((ep.ld_c_src & 3) == 0 && al(ep.c_src))) &&
          (!ep.act_out || ((ep.ld_act & 3) == 0 && al(ep.act_out)));
 }
+// One output of the epilogue: the arithmetic every form of it spells (gemm_epilogue above, the 16-byte form below, the split-K reduction); the
+// element-wise loop of the register-staged kernel's 32-row tile calls it.  Explicit fused multiply-adds: the same rounding wherever this is
+// compiled, whatever contraction the optimiser would pick.  c_old() is only called on the (uniform) side that reads memory, so a caller may
+// put the load itself in it.
+template <class COld>
+__device__ __forceinline__ float gemm_epilogue_value(const GemmArgs &g, float acc, COld &&c_old, float bias) {
+  const aslp_gemm_epilogue &ep = g.ep;
+  float t = (ep.W != nullptr || g.beta != 0.0f) ? fmaf(g.alpha, acc, fmaf(g.beta, c_old(), bias)) : fmaf(g.alpha, acc, bias);
+  if (ep.clip > 0.0f) t = fminf(fmaxf(t, -ep.clip), ep.clip);
+  return t;
+}
 // one lane's 4 consecutive outputs of a row (columns col .. col+3): the arithmetic of the epilogue ...
 typedef float f32x4v __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ void gemm_epilogue_value4(const GemmArgs &g, float4 acc4, float4 c_old, float4 w_old, float4 bias, f32x4v *out, float4 *wn) {
@@ -238,8 +249,7 @@ __device__ __forceinline__ void gemm_epilogue_value4(const GemmArgs &g, float4 a
   const float co[4] = {c_old.x, c_old.y, c_old.z, c_old.w}, bs[4] = {bias.x, bias.y, bias.z, bias.w};
 #pragma unroll
   for (int q = 0; q < 4; q++) {
-    // explicit fused multiply-adds: the same rounding wherever this arithmetic is compiled (the narrow epilogue, the split-K
-    // reduction and the register-staged kernel spell it the same way), whatever contraction the optimiser would pick
+    // gemm_epilogue_value, written out: called from here it moves the machine code of 17 split-fp16 kernels (same arithmetic, other schedule)
     float t = (ep.W != nullptr || g.beta != 0.0f) ? fmaf(g.alpha, o[q], fmaf(g.beta, co[q], bs[q])) : fmaf(g.alpha, o[q], bs[q]);
     if (ep.clip > 0.0f) t = fminf(fmaxf(t, -ep.clip), ep.clip);
     o[q] = t;
