@@ -216,6 +216,11 @@ typedef struct aslp_gemm_epilogue_ {
    * NULL when beta == 0) the previous step left, the bounds of its two operands' planes and K. */
   const float *bound_w_parts, *bound_c_parts;
   int bound_n;
+  /* one maximum per workgroup of |act(v)|, the values stored to act_out (NULL, or aslp_gemm_last_parts() floats; honoured like cmax_parts,
+   * and only with act_out set): for an activation without a bound known before the launch (ReLU: max |C| would also count the
+   * negative values and scale the planes by a looser bound) -- the consumer converts act_out with these as its bound, without a
+   * maximum pass.  Last member: a zero-initialised epilogue keeps its meaning. */
+  float *amax_parts;
 } aslp_gemm_epilogue;
 /* number of per-workgroup maxima (and proof that the planes were written) of the calling thread's latest aslp_sgemm* call; 0 = the kernel that
  * ran does not leave them */
@@ -278,6 +283,10 @@ int aslp_gemm_split16_ragged_get(void);
 aslp_planes *aslp_planes_new(void);
 void aslp_planes_free(aslp_planes *p);
 int aslp_planes_convert(aslp_planes *p, const float *src, MatrixDim d);
+/* ... without the maximum pass: the kernel that wrote src left n_parts per-workgroup maxima of |src| in p's own parts array (the `parts` of
+ * aslp_planes_as_output -- e.g. given to a product as aslp_gemm_epilogue.amax_parts / cmax_parts, n_parts = aslp_gemm_last_parts()).  One
+ * streaming launch; what the engine's PlaneHolder::Of does with a producer's maxima.  -2 = refused. */
+int aslp_planes_convert_with_parts(aslp_planes *p, const float *src, MatrixDim d, int n_parts);
 /* aslp_sgemm_ex with the planes of A and / or B (NULL: that operand is converted inside the call); the planes must be those of the
  * matrix the fp32 pointer names.  Runs on the fp32 instruction like aslp_sgemm_ex when aslp_gemm_split16 is off or the shape is not
  * served. */
@@ -426,6 +435,14 @@ void aslp_xent_sum_rowstats(const double *rowstats, int rows, int batches, doubl
  * planes were written, 0 if only eout was (operands not 16-byte aligned, no maxima). */
 int aslp_diff_sigmoid_p(float *eout, const float *e, const float *y, MatrixDim d, int e_stride, int y_stride, const float *e_max_parts, int n_parts,
                         const aslp_planes_out *out_planes);
+/* The same for ReLU and Tanh: in-diff and its two planes in one launch, bound max |out_diff| (both derivatives are <= 1) from the n_parts
+ * per-workgroup maxima the producer of out_diff left.  The in-diff values are those of aslp_diff_relu (mask: heaviside of the
+ * PRE-activation `in`) / cudaF_diff_tanh (y: the activation), bit for bit.  Returns 1 if in-diff and planes were written; 0 = not served
+ * (operands not 16-byte aligned, no maxima, no planes): NOTHING was launched and the caller runs the plain kernel. */
+int aslp_diff_relu_p(float *in_diff, const float *in, const float *out_diff, MatrixDim d, int in_stride, int od_stride, const float *od_max_parts,
+                     int n_parts, const aslp_planes_out *out_planes);
+int aslp_diff_tanh_p(float *eout, const float *e, const float *y, MatrixDim d, int e_stride, int y_stride, const float *e_max_parts, int n_parts,
+                     const aslp_planes_out *out_planes);
 /* PosteriorToMatrix scatter: mat[row[i]][col[i]] += val[i]  (hmm/posterior.cc, used nnet-loss.cc:168) */
 void aslp_scatter_add(float *mat, MatrixDim d, const int32_cuda *rows, const int32_cuda *cols, const float *vals, int n);
 /* Splice backward (nnet-various.h:143-175): in_diff[t] = sum_k out_diff[clamp(t+off[k])][k-th block] */

@@ -59,6 +59,10 @@ enum {
   ASLP_RECURRENT_UNFUSED = 3      /* a product and cell kernels per timestep (csrc/rnn_cells.hip) */
 };
 int aslp_recurrent_last_path(int backward);
+/* How many Tanh / ReLU components took their output from the epilogue of the layer product in front of them in n's latest Propagate
+ * (Sigmoid layers, which have always done so, are not counted).  0 under aslp_nnet_set_layer_fusion(n, 0) and under the A/B switch
+ * ASLP_FUSE_TANH_RELU=0 (read once per process), which sends these two activations through their own launches.  For tests. */
+int aslp_nnet_last_fused_activations(aslp_nnet_t n);
 
 /* Nnet::GetParams (:296) -> host buffer of NumParams floats */
 int aslp_nnet_get_params(aslp_nnet_t n, float *host_buf, int buf_len);

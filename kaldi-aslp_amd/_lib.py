@@ -30,7 +30,7 @@ class GemmEpilogue(C.Structure):
                 ("colsum", C.c_void_p), ("colsum_beta", C.c_float), ("colsum_w", C.c_void_p), ("colsum_w_alpha", C.c_float),
                 ("colstats", C.c_void_p), ("colstats_ld", C.c_int), ("c_src", C.c_void_p), ("ld_c_src", C.c_int),
                 ("planes", PlanesOut), ("planes_of", C.c_int), ("wmax_parts", C.c_void_p), ("cmax_parts", C.c_void_p),
-                ("bound_w_parts", C.c_void_p), ("bound_c_parts", C.c_void_p), ("bound_n", C.c_int)]
+                ("bound_w_parts", C.c_void_p), ("bound_c_parts", C.c_void_p), ("bound_n", C.c_int), ("amax_parts", C.c_void_p)]
 
 
 class GruSeq(C.Structure):
@@ -180,6 +180,7 @@ _sig("aslp_gemm_split16_ragged_get", _i)
 _sig("aslp_planes_new", _vp)
 _sig("aslp_planes_free", None, _vp)
 _sig("aslp_planes_convert", _i, _vp, _vp, _md)
+_sig("aslp_planes_convert_with_parts", _i, _vp, _vp, _md, _i)
 _sig("aslp_planes_reserve", None, _vp, _i, _i)
 _sig("aslp_copy_mat_planes", _i, _vp, _md, _vp, _i, C.POINTER(PlanesOut))
 _sig("aslp_planes_as_output", None, _vp, C.POINTER(PlanesOut))
@@ -270,6 +271,9 @@ _sig("aslp_rnn_vec_grads", None, C.POINTER(RnnVecGrad), _i, _i, _i, _f, _f, _f)
 _sig("aslp_scatter_add", None, _vp, _md, _vp, _vp, _vp, _i)
 _sig("aslp_splice_backward", None, _vp, _md, _vp, _i, _vp, _i)
 _sig("aslp_diff_relu", None, _vp, _vp, _vp, _md, _i, _i)
+_sig("aslp_diff_sigmoid_p", _i, _vp, _vp, _vp, _md, _i, _i, _vp, _i, C.POINTER(PlanesOut))
+_sig("aslp_diff_relu_p", _i, _vp, _vp, _vp, _md, _i, _i, _vp, _i, C.POINTER(PlanesOut))
+_sig("aslp_diff_tanh_p", _i, _vp, _vp, _vp, _md, _i, _i, _vp, _i, C.POINTER(PlanesOut))
 _sig("aslp_max_norm_rows", None, _vp, _md, _f)
 
 

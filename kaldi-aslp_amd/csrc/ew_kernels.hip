@@ -99,35 +99,57 @@ struct DiffTanh { __device__ float operator()(float, float e, float y, int, int)
 struct DiffRelu { __device__ float operator()(float, float in, float od, int, int) const { return in > 0.0f ? od : 0.0f; } };
 struct CopyMat { __device__ float operator()(float, float a, float, int, int) const { return a; } };
 
-// Sigmoid backward which also leaves the fp16 planes of its result (csrc/split16.h): |e y (1 - y)| <= max |e| / 4, and the maxima of |e| come
-// with e from the kernel that wrote it (n_parts per-workgroup values), so the scale is known before the first element is written.  The
-// arithmetic of an element is DiffSigmoid's.  Workgroup 0 stores the bound for the planes' readers.
-__global__ void __launch_bounds__(kBlock) diff_sigmoid_planes_kernel(float *__restrict__ eout, int ldo, const float *__restrict__ e, int lde,
-                                                                     const float *__restrict__ y, int ldy, int rows, int cols4,
-                                                                     const float *__restrict__ e_max_parts, int n_parts, S16Out po) {
+// Activation backward passes which also leave the fp16 planes of their result (csrc/split16.h), written once over the element functor F
+// (DiffSigmoid, DiffTanh, DiffRelu: the arithmetic of an element is the plain kernel's; a, b are its two operands in its own order).
+// |in-diff| <= kBound max |out-diff| -- 1/4 for the sigmoid (y (1 - y) <= 1/4), 1 for tanh (1 - y^2 <= 1) and ReLU (a 0 / 1 mask) -- and the
+// maxima of the out-diff come with it from the kernel that wrote it (n_parts per-workgroup values), so the scale is known before the first
+// element is written.  Workgroup 0 stores the bound for the planes' readers.
+template <class F> struct DiffBound;
+template <> struct DiffBound<DiffSigmoid> { static constexpr float k = 0.25f; };
+template <> struct DiffBound<DiffTanh> { static constexpr float k = 1.0f; };
+template <> struct DiffBound<DiffRelu> { static constexpr float k = 1.0f; };
+template <class F>
+__global__ void __launch_bounds__(kBlock) diff_act_planes_kernel(float *__restrict__ eout, int ldo, const float *__restrict__ a, int lda,
+                                                                 const float *__restrict__ b, int ldb, int rows, int cols4,
+                                                                 const float *__restrict__ od_max_parts, int n_parts, S16Out po) {
   __shared__ float wm[kBlock / 64];
   float m = 0.f;
-  for (int i = threadIdx.x; i < n_parts; i += kBlock) m = fmaxf(m, e_max_parts[i]);
+  for (int i = threadIdx.x; i < n_parts; i += kBlock) m = fmaxf(m, od_max_parts[i]);
   m = wave_max(m);
   if ((threadIdx.x & 63) == 0) wm[threadIdx.x >> 6] = m;
   __syncthreads();
   m = wm[0];
   for (int w = 1; w < kBlock / 64; w++) m = fmaxf(m, wm[w]);
-  const float bound = 0.25f * m;
+  const float bound = DiffBound<F>::k * m;
   if (blockIdx.x == 0 && threadIdx.x == 0) *const_cast<unsigned *>(po.slot) = __float_as_uint(bound);
   const float s = ldexpf(1.f, s16_exponent(__float_as_uint(bound)));
-  const DiffSigmoid f{};
+  const F f{};
   const long n = (long)rows * cols4;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
     const int r = (int)(i / cols4), c = (int)(i - (long)r * cols4) * 4;
-    const float4 ev = *reinterpret_cast<const float4 *>(e + (long)r * lde + c), yv = *reinterpret_cast<const float4 *>(y + (long)r * ldy + c);
-    const float4 o = make_float4(f(0.f, ev.x, yv.x, r, c), f(0.f, ev.y, yv.y, r, c + 1), f(0.f, ev.z, yv.z, r, c + 2), f(0.f, ev.w, yv.w, r, c + 3));
+    const float4 av = *reinterpret_cast<const float4 *>(a + (long)r * lda + c), bv = *reinterpret_cast<const float4 *>(b + (long)r * ldb + c);
+    const float4 o = make_float4(f(0.f, av.x, bv.x, r, c), f(0.f, av.y, bv.y, r, c + 1), f(0.f, av.z, bv.z, r, c + 2), f(0.f, av.w, bv.w, r, c + 3));
     *reinterpret_cast<float4 *>(eout + (long)r * ldo + c) = o;
     half4 hi, lo;
     s16_split4(o, s, &hi, &lo);
     *reinterpret_cast<half4 *>(po.hi + (long)r * po.ld + c) = hi;
     *reinterpret_cast<half4 *>(po.lo + (long)r * po.ld + c) = lo;
   }
+}
+// the launch, where the operands allow 16-byte accesses and maxima and planes are there; false: nothing was launched
+template <class F>
+bool launch_diff_act_planes(const char *name, float *eout, MatrixDim d, const float *a, int lda, const float *b, int ldb, const float *od_max_parts,
+                            int n_parts, const aslp_planes_out *out_planes) {
+  const bool vec = d.rows > 0 && d.cols > 0 && d.cols % 4 == 0 && d.stride % 4 == 0 && lda % 4 == 0 && ldb % 4 == 0 && aligned16(eout) &&
+                   aligned16(a) && aligned16(b);
+  if (!vec || !od_max_parts || n_parts <= 0 || !out_planes || !out_planes->hi || !out_planes->lo || !out_planes->slot || out_planes->ld < d.cols)
+    return false;
+  S16Out po = {static_cast<h16 *>(out_planes->hi), static_cast<h16 *>(out_planes->lo), out_planes->ld, out_planes->slot, nullptr};
+  const long n = (long)d.rows * (d.cols / 4);
+  hipLaunchKernelGGL(diff_act_planes_kernel<F>, dim3(grid_for(n)), dim3(kBlock), 0, cur_stream(), eout, d.stride, a, lda, b, ldb, d.rows, d.cols / 4,
+                     od_max_parts, n_parts, po);
+  check_launch(name);
+  return true;
 }
 
 // transposed AddMat (rare; cu-kernels.cu:584 A_trans branch)
@@ -418,18 +440,18 @@ void cudaF_diff_sigmoid(aslp_dim3, aslp_dim3, float *eout, const float *e, const
 }
 int aslp_diff_sigmoid_p(float *eout, const float *e, const float *y, MatrixDim d, int e_stride, int y_stride, const float *e_max_parts, int n_parts,
                         const aslp_planes_out *out_planes) {
-  const bool vec = d.rows > 0 && d.cols > 0 && d.cols % 4 == 0 && d.stride % 4 == 0 && e_stride % 4 == 0 && y_stride % 4 == 0 && aligned16(eout) &&
-                   aligned16(e) && aligned16(y);
-  if (!vec || !e_max_parts || n_parts <= 0 || !out_planes || !out_planes->hi || !out_planes->slot || out_planes->ld < d.cols) {
-    cudaF_diff_sigmoid(aslp_dim3(), aslp_dim3(), eout, e, y, d, e_stride, y_stride);
-    return 0;
-  }
-  S16Out po = {static_cast<h16 *>(out_planes->hi), static_cast<h16 *>(out_planes->lo), out_planes->ld, out_planes->slot, nullptr};
-  const long n = (long)d.rows * (d.cols / 4);
-  hipLaunchKernelGGL(diff_sigmoid_planes_kernel, dim3(grid_for(n)), dim3(kBlock), 0, cur_stream(), eout, d.stride, e, e_stride, y, y_stride, d.rows,
-                     d.cols / 4, e_max_parts, n_parts, po);
-  check_launch("diff_sigmoid_planes");
-  return 1;
+  if (launch_diff_act_planes<DiffSigmoid>("diff_sigmoid_planes", eout, d, e, e_stride, y, y_stride, e_max_parts, n_parts, out_planes)) return 1;
+  cudaF_diff_sigmoid(aslp_dim3(), aslp_dim3(), eout, e, y, d, e_stride, y_stride);
+  return 0;
+}
+// (these two launch nothing when they cannot leave the planes: the caller runs the plain kernel)
+int aslp_diff_tanh_p(float *eout, const float *e, const float *y, MatrixDim d, int e_stride, int y_stride, const float *e_max_parts, int n_parts,
+                     const aslp_planes_out *out_planes) {
+  return launch_diff_act_planes<DiffTanh>("diff_tanh_planes", eout, d, e, e_stride, y, y_stride, e_max_parts, n_parts, out_planes) ? 1 : 0;
+}
+int aslp_diff_relu_p(float *in_diff, const float *in, const float *out_diff, MatrixDim d, int in_stride, int od_stride, const float *od_max_parts,
+                     int n_parts, const aslp_planes_out *out_planes) {
+  return launch_diff_act_planes<DiffRelu>("diff_relu_planes", in_diff, d, in, in_stride, out_diff, od_stride, od_max_parts, n_parts, out_planes) ? 1 : 0;
 }
 void cudaF_diff_tanh(aslp_dim3, aslp_dim3, float *eout, const float *e, const float *y, MatrixDim d, int e_stride, int y_stride) {
   launch_map<false>("diff_tanh", eout, d, e, e_stride, y, y_stride, DiffTanh{});

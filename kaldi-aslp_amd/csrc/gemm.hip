@@ -459,7 +459,10 @@ static int sgemm_impl(int transA, int transB, int M, int N, int K, float alpha, 
     g.ep.colstats = nullptr;   // formed in its epilogue, like the column sums of a transposed A
     g.ep.colsum = nullptr;
     t_last_cfg = gemm_split16_last_tile();
-  } else launch_layout(g, transA != 0, transB != 0);
+  } else {
+    g.ep.amax_parts = nullptr;   // the fp32 instruction's kernels leave no maxima of the activation output (aslp_gemm_last_parts() == 0)
+    launch_layout(g, transA != 0, transB != 0);
+  }
   if (g.ep.colstats) {  // the chosen kernel does not form them in its epilogue: one pass over the finished C
     const int groups = (M + 31) / 32;
     hipLaunchKernelGGL(colstats_kernel, dim3((N + 63) / 64, groups), dim3(64), 0, cur_stream(), C, ldc, M, N, g.ep.colstats, g.ep.colstats_ld, groups);
@@ -486,6 +489,14 @@ int aslp_planes_convert(aslp_planes *p, const float *src, MatrixDim d) {
   if (!p || !src) return -1;
   const bool ok = reinterpret_cast<PlaneSet *>(p)->ConvertFrom(src, d.rows, d.cols, d.stride);
   check_launch("aslp_planes_convert");
+  return ok ? 0 : -2;
+}
+int aslp_planes_convert_with_parts(aslp_planes *p, const float *src, MatrixDim d, int n_parts) {
+  if (!p || !src || n_parts <= 0) return -1;
+  PlaneSet *ps = reinterpret_cast<PlaneSet *>(p);
+  if (!ps->Parts()) return -2;   // (the maxima were to be left in the set's own array)
+  const bool ok = ps->ConvertWithParts(src, d.rows, d.cols, d.stride, n_parts);
+  check_launch("aslp_planes_convert_with_parts");
   return ok ? 0 : -2;
 }
 void aslp_planes_reserve(aslp_planes *p, int rows, int cols) { if (p) reinterpret_cast<PlaneSet *>(p)->Reserve(rows, cols); }
@@ -543,6 +554,7 @@ int aslp::sgemm_pair_views(int transA, int transB, int M, int N, int K, float al
     book_launch(layout_slot(transA != 0, transB != 0), 2, M, N, K);
     return 0;
   }
+  g.ep.amax_parts = g.ep1.amax_parts = nullptr;   // (as sgemm_impl)
   launch_layout(g, transA != 0, transB != 0);
   if (t_last_cfg < 0) return two();
   check_launch("aslp_sgemm_pair");

@@ -93,10 +93,10 @@ __device__ __forceinline__ void xcd_tile(const GemmArgs &g, int &tm, int &tn, in
 }
 
 // What an epilogue leaves for the split-fp16 products that will read its output (aslp_gemm_epilogue.planes / *_parts), per wave:
-// the scale of the planes it writes (0: none) and the running maxima of |W after the step| and |C|.
+// the scale of the planes it writes (0: none) and the running maxima of |W after the step|, |C| and (amax_parts) |act_out|.
 struct EpiExtra {
   float pscale = 0.f;
-  float wmax = 0.f, cmax = 0.f;
+  float wmax = 0.f, cmax = 0.f, amax = 0.f;
 };
 __device__ __forceinline__ float epi_finite_abs(float v) { const float a = fabsf(v); return a < 3.0e38f ? a : 0.f; }
 __device__ __forceinline__ void epi_plane_store(const aslp_gemm_epilogue &ep, float scale, float v, long row, int col) {
@@ -259,7 +259,9 @@ __device__ __forceinline__ void gemm_epilogue_value4(const GemmArgs &g, float4 a
   wn->z = fmaf(ep.w_alpha, o[2], w_old.z); wn->w = fmaf(ep.w_alpha, o[3], w_old.w);
 }
 // ... and its stores
-__device__ __forceinline__ void gemm_epilogue_store4(const GemmArgs &g, const f32x4v &out, const float4 &wn, int row, int col, float pscale = 0.f) {
+// (amax: where the running maximum of |act_out| is kept, or NULL)
+__device__ __forceinline__ void gemm_epilogue_store4(const GemmArgs &g, const f32x4v &out, const float4 &wn, int row, int col, float pscale = 0.f,
+                                                     float *amax = nullptr) {
   const aslp_gemm_epilogue &ep = g.ep;
   if (pscale != 0.f && ep.planes_of == 1 && ep.W) epi_plane_store4(ep, pscale, wn, row, col);
   f32x4v *cp = reinterpret_cast<f32x4v *>(g.C + (long)row * g.ldc + col);
@@ -272,6 +274,7 @@ __device__ __forceinline__ void gemm_epilogue_store4(const GemmArgs &g, const f3
     for (int q = 0; q < 4; q++) a[q] = ep.act == 1 ? sigmoid_ref(out[q]) : ep.act == 2 ? tanh_ref(out[q]) : ep.act == 3 ? fmaxf(out[q], 0.0f) : out[q];
     *reinterpret_cast<float4 *>(ep.act_out + (long)row * ep.ld_act + col) = make_float4(a[0], a[1], a[2], a[3]);
     if (pscale != 0.f && ep.planes_of == 2) epi_plane_store4(ep, pscale, make_float4(a[0], a[1], a[2], a[3]), row, col);
+    if (amax) *amax = fmaxf(*amax, fmaxf(fmaxf(epi_finite_abs(a[0]), epi_finite_abs(a[1])), fmaxf(epi_finite_abs(a[2]), epi_finite_abs(a[3]))));
   }
 }
 
@@ -346,7 +349,7 @@ __device__ __forceinline__ void gemm_epilogue_wide(const GemmArgs &g, const f32x
         for (int j = 0; j < 4; j++) {
           const int row = row0 + i * 32 + rr + 8 * j;
           if (!colok || row >= g.M) continue;
-          gemm_epilogue_store4(g, out[j], wn[j], row, col, track ? x.pscale : 0.f);
+          gemm_epilogue_store4(g, out[j], wn[j], row, col, track ? x.pscale : 0.f, (track && ep.amax_parts != nullptr) ? &x.amax : nullptr);
           if (track) {
             x.cmax = fmaxf(x.cmax, fmaxf(fmaxf(epi_finite_abs(out[j][0]), epi_finite_abs(out[j][1])), fmaxf(epi_finite_abs(out[j][2]), epi_finite_abs(out[j][3]))));
             if (ep.W) x.wmax = s16_absmax4(x.wmax, wn[j]);

@@ -308,7 +308,7 @@ __global__ void __launch_bounds__(kBlock) splitk_reduce_kernel(const float *__re
   // what a split-fp16 product leaves for the products that read its output (aslp_gemm_epilogue.planes / cmax_parts): the planes of the
   // activation output under a bound known before the launch, one maximum of |C| per workgroup
   const float pscale = (g.ep.planes_of == 2 && g.ep.planes.hi != nullptr && g.ep.act_out != nullptr) ? ldexpf(1.f, s16_exponent(*g.ep.planes.slot)) : 0.f;
-  float cmax = 0.f;
+  float cmax = 0.f, amax = 0.f;   // (amax: of |act_out|, for aslp_gemm_epilogue.amax_parts)
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
     const int row = (int)(i / g.N), col = (int)(i - (long)row * g.N);
     float acc = part[i];
@@ -326,6 +326,7 @@ __global__ void __launch_bounds__(kBlock) splitk_reduce_kernel(const float *__re
       const float a = g.ep.act == 1 ? sigmoid_ref(v) : g.ep.act == 2 ? tanh_ref(v) : g.ep.act == 3 ? fmaxf(v, 0.0f) : v;
       g.ep.act_out[(long)row * g.ep.ld_act + col] = a;
       if (pscale != 0.f) epi_plane_store(g.ep, pscale, a, row, col);
+      amax = fmaxf(amax, epi_finite_abs(a));
     }
   }
   if (g.ep.cmax_parts != nullptr) {   // (uniform)
@@ -337,6 +338,17 @@ __global__ void __launch_bounds__(kBlock) splitk_reduce_kernel(const float *__re
       float m = wmax[0];
       for (int w = 1; w < kBlock / 64; w++) m = fmaxf(m, wmax[w]);
       g.ep.cmax_parts[(long)blockIdx.y * gridDim.x + blockIdx.x] = m;
+    }
+  }
+  if (g.ep.amax_parts != nullptr && g.ep.act_out != nullptr) {   // (uniform)
+    __shared__ float wamax[kBlock / 64];
+    amax = wave_max(amax);
+    if ((threadIdx.x & 63) == 0) wamax[threadIdx.x >> 6] = amax;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      float m = wamax[0];
+      for (int w = 1; w < kBlock / 64; w++) m = fmaxf(m, wamax[w]);
+      g.ep.amax_parts[(long)blockIdx.y * gridDim.x + blockIdx.x] = m;
     }
   }
 }

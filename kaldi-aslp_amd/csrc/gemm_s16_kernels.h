@@ -117,6 +117,20 @@ __device__ __forceinline__ void s16_finish(const GemmArgs &g, const S16View &va,
       if (g.ep.cmax_parts) g.ep.cmax_parts[idx] = c;
     }
   }
+  // ... and of |act_out| (amax_parts: an activation without a bound known before the launch).  Words of their own behind the 2 NW above,
+  // which thread 0 may still be reading
+  if (EXTRA && g.ep.amax_parts != nullptr) {   // (uniform)
+    const float amx = wave_max(xtra.amax);
+    __builtin_amdgcn_s_barrier();   // every wave is done with its epilogue slice of the LDS
+    if (lane == 0) lds[2 * NW + wave] = amx;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      float a = lds[2 * NW];
+#pragma unroll
+      for (int q = 1; q < NW; q++) a = fmaxf(a, lds[2 * NW + q]);
+      g.ep.amax_parts[(int)blockIdx.z * (int)gridDim.x + (int)blockIdx.x] = a;
+    }
+  }
 }
 // column sums of a reduction-major A from the fragments a wave multiplies anyway: sum over the 8 k of a fragment of hi + 2^-11 lo'
 __device__ __forceinline__ float s16_frag_sum(float sum, const half8 hi, const half8 lo) {

@@ -245,7 +245,7 @@ const S16Tuning &s16_tuning() {
   return t;
 }
 // what one epilogue asks the product to leave behind, and whether the 16-byte epilogue applies to it
-struct S16Asks { int planes_of = 0; bool wmax = false, cmax = false, colstats = false, colsum = false, wide_ok = false; };
+struct S16Asks { int planes_of = 0; bool wmax = false, cmax = false, amax = false, colstats = false, colsum = false, wide_ok = false; };
 // the decision.  tile: 304 = 32 x 64, 305 = the same with four stages (tuning aid), 308 = 64 x 128, 311 = 128 x 128 (gemm_s16_glds),
 // 328 = 128 x 128 both operands reduction-major (gemm_s16_ks128), 351 = 128 x 128 with producer / consumer waves (gemm_s16_pc); one-plane
 // products 404 / 408 / 411; 0 = not served.  split_k > 1: K in chunks of k_chunk over blockIdx.y on tile 308 / 408 with emptied epilogues,
@@ -308,7 +308,7 @@ S16Plan s16_plan(int M, int N, int K, bool a_kc, bool b_kc, bool pair, S16Asks e
   if (!pair) ep1 = S16Asks();
   // planes / maxima of the output are written by the 16-byte epilogue only: where that does not apply the request is dropped (the
   // caller sees aslp_gemm_last_parts() == 0 and converts for itself)
-  auto drop_extras = [](S16Asks &e) { e.planes_of = 0; e.wmax = e.cmax = false; };
+  auto drop_extras = [](S16Asks &e) { e.planes_of = 0; e.wmax = e.cmax = e.amax = false; };
   p.drop_extras = !ep.wide_ok;
   p.drop_extras1 = pair && !ep1.wide_ok;
   if (p.drop_extras) drop_extras(ep);
@@ -321,14 +321,14 @@ S16Plan s16_plan(int M, int N, int K, bool a_kc, bool b_kc, bool pair, S16Asks e
   // that leaves none (the smallest tile of such a grid is 64 x 128), and planes of updated weights, whose bound is formed from maxima, go too
   p.drop_maxima = tiles > kS16MaxParts;
   if (p.drop_maxima) {
-    auto drop_maxima = [](S16Asks &e) { if (e.planes_of == 1) e.planes_of = 0; e.wmax = e.cmax = false; };
+    auto drop_maxima = [](S16Asks &e) { if (e.planes_of == 1) e.planes_of = 0; e.wmax = e.cmax = e.amax = false; };
     drop_maxima(ep);
     drop_maxima(ep1);
   }
-  const bool leaves = ep.planes_of != 0 || ep.wmax || ep.cmax, leaves1 = ep1.planes_of != 0 || ep1.wmax || ep1.cmax;
+  const bool leaves = ep.planes_of != 0 || ep.wmax || ep.cmax || ep.amax, leaves1 = ep1.planes_of != 0 || ep1.wmax || ep1.cmax || ep1.amax;
   const bool extras = leaves || ep.colstats || ep.colsum || leaves1 || ep1.colstats || ep1.colsum;
   // (act_out planes asked for by a forward product are given up for the split: the consumer converts the small activation matrix itself)
-  // (the second launch writes the planes of an activation output and the maxima of |C| itself: those two requests go with the split)
+  // (the second launch writes the planes of an activation output and the maxima of |C| and of |act_out| itself: those requests go with the split)
   const bool reduce_serves = !ep.wmax && !ep.colstats && !ep.colsum && ep.planes_of != 1 && !pair;
   // ... unless 32 x 64 tiles fill the chip in ONE round with the whole reduction (256 x 2048 outputs: 15.2 us against 19.4 us for the
   // two launches of the split; the epilogue, with whatever it was asked to leave, stays in the product's launch)
@@ -583,22 +583,25 @@ bool gemm_split16_planes_launch(GemmArgs &g, bool a_kc, bool b_kc, const S16View
     g1.C = C; g1.ep = ep;
     S16Asks s;
     s.planes_of = ep.planes_of; s.wmax = ep.wmax_parts != nullptr; s.cmax = ep.cmax_parts != nullptr;
+    s.amax = ep.amax_parts != nullptr && ep.act_out != nullptr;
     s.colstats = ep.colstats != nullptr; s.colsum = ep.colsum != nullptr;
     s.wide_ok = g.wide_epilogue && gemm_epilogue_wide_ok(g1);
     return s;
   };
   S16Plan p = s16_plan(g.M, g.N, g.K, a_kc, b_kc, g.pair != 0, asks(g.ep, g.C), g.pair ? asks(g.ep1, g.C1) : S16Asks(), planes, cfg, s16_tuning());
-  auto drop_extras = [](aslp_gemm_epilogue &ep) { ep.planes_of = 0; ep.wmax_parts = ep.cmax_parts = nullptr; ep.bound_w_parts = ep.bound_c_parts = nullptr; };
+  auto drop_extras = [](aslp_gemm_epilogue &ep) { ep.planes_of = 0; ep.wmax_parts = ep.cmax_parts = ep.amax_parts = nullptr; ep.bound_w_parts = ep.bound_c_parts = nullptr; };
   auto drop_maxima = [](aslp_gemm_epilogue &ep) {
     if (ep.planes_of == 1) { ep.planes_of = 0; ep.bound_w_parts = ep.bound_c_parts = nullptr; }
-    ep.wmax_parts = ep.cmax_parts = nullptr;
+    ep.wmax_parts = ep.cmax_parts = ep.amax_parts = nullptr;
   };
+  if (g.ep.act_out == nullptr) g.ep.amax_parts = nullptr;   // (maxima of an output that is not written)
+  if (g.ep1.act_out == nullptr) g.ep1.amax_parts = nullptr;
   if (p.drop_extras) drop_extras(g.ep);
   if (p.drop_extras1) drop_extras(g.ep1);
   if (p.drop_maxima) { drop_maxima(g.ep); if (g.pair) drop_maxima(g.ep1); }
   auto launch = [&](GemmArgs &ga, int tile) {
-    const bool extra = ga.ep.planes_of != 0 || ga.ep.wmax_parts != nullptr || ga.ep.cmax_parts != nullptr ||
-                       (ga.pair && (ga.ep1.planes_of != 0 || ga.ep1.wmax_parts || ga.ep1.cmax_parts));
+    const bool extra = ga.ep.planes_of != 0 || ga.ep.wmax_parts != nullptr || ga.ep.cmax_parts != nullptr || ga.ep.amax_parts != nullptr ||
+                       (ga.pair && (ga.ep1.planes_of != 0 || ga.ep1.wmax_parts || ga.ep1.cmax_parts || ga.ep1.amax_parts));
     if (a_kc && b_kc) s16_launch_tile<true, true>(ga, ops, tile, extra);
     else if (a_kc && !b_kc) s16_launch_tile<true, false>(ga, ops, tile, extra);
     else if (!a_kc && !b_kc) s16_launch_tile<false, false>(ga, ops, tile, extra);
@@ -618,7 +621,7 @@ bool gemm_split16_planes_launch(GemmArgs &g, bool a_kc, bool b_kc, const S16View
       GemmArgs r = g;
       r.split_k = 0;
       const int wgs = gemm_splitk_reduce(part, p.split_k, stride, r);
-      t_last_parts = (r.ep.planes_of == 2 || r.ep.cmax_parts) ? wgs : 0;
+      t_last_parts = (r.ep.planes_of == 2 || r.ep.cmax_parts || r.ep.amax_parts) ? wgs : 0;
       return true;
     }
     S16Tuning whole = s16_tuning();   // no scratch for the chunks: the product in one launch
@@ -700,6 +703,7 @@ int aslp_gemm_split16_plan(int transA, int transB, int M, int N, int K, int ldc,
     if (e) {
       g.ep = *e;
       s.planes_of = e->planes_of; s.wmax = e->wmax_parts != nullptr; s.cmax = e->cmax_parts != nullptr;
+      s.amax = e->amax_parts != nullptr && e->act_out != nullptr;
       s.colstats = e->colstats != nullptr; s.colsum = e->colsum != nullptr;
     }
     s.wide_ok = gemm_epilogue_wide_ok(g);

@@ -155,6 +155,7 @@ int aslp_nnet_set_seq_lengths(aslp_nnet_t n, const int32_t *lens, int ns) {
 }
 int aslp_nnet_set_chunk_size(aslp_nnet_t n, int chunk_size) { API_BEGIN n->nnet.SetChunkSize(chunk_size); API_END }
 int aslp_recurrent_last_path(int backward) { return LastRecurrentPath(backward); }
+int aslp_nnet_last_fused_activations(aslp_nnet_t n) { return n ? n->nnet.LastFusedActivations() : -1; }
 
 int aslp_nnet_get_params(aslp_nnet_t n, float *host_buf, int buf_len) {
   API_BEGIN

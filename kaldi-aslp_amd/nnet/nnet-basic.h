@@ -220,27 +220,36 @@ class AffineTransform : public UpdatableComponent {
   // Executor peephole (nnet-nnet.cpp): the next Propagate also forms the per-column statistics of its output for the
   // BatchNormalization behind it, in `buf` as aslp_gemm_epilogue.colstats lays them out (groups = ceil(rows / 32), ld = dim rounded to 4)
   void RequestOutputStats(CuVectorD *buf) { stats_request_ = buf; }
-  // Executor peephole (nnet-nnet.cpp): a Sigmoid that is this component's only consumer gets its output from the same
-  // GEMM (second store of the epilogue, sigmoid of the value just written to `out`): same bits as the separate launch.
-  // act_planes: the AffineTransform that alone reads sigmoid_out wants its fp16 planes (bound 1): the same epilogue writes them
-  void PropagateWithSigmoid(const CuMatrixBase &in, CuMatrix *out, CuMatrix *sigmoid_out, PlaneHolder *act_planes = nullptr) {
+  // Executor peephole (nnet-nnet.cpp): a Sigmoid, Tanh or ReLU that is this component's only consumer gets its output from the same
+  // GEMM (second store of the epilogue, the activation of the value just written to `out`): same bits as the separate launch.
+  // act: the epilogue's number of the activation (aslp_gemm_epilogue.act: 1 sigmoid, 2 tanh, 3 relu).
+  // act_planes: the AffineTransform that alone reads act_out wants its fp16 planes.  Sigmoid and Tanh have the bound 1: the same epilogue
+  // writes the planes.  ReLU has no bound before the launch: the epilogue leaves the per-workgroup maxima of act_out with the consumer,
+  // whose conversion (PlaneHolder::Of) then needs no maximum pass.
+  void PropagateWithActivation(const CuMatrixBase &in, CuMatrix *out, CuMatrix *act_out, int act, PlaneHolder *act_planes = nullptr) {
     ASLP_ASSERT(in.NumCols() == input_dim_);
+    ASLP_ASSERT(act >= 1 && act <= 3);
     if (out->NumRows() != in.NumRows() || out->NumCols() != output_dim_) out->Resize(in.NumRows(), output_dim_, kUndefined);
-    if (sigmoid_out->NumRows() != in.NumRows() || sigmoid_out->NumCols() != output_dim_) sigmoid_out->Resize(in.NumRows(), output_dim_, kUndefined);
+    if (act_out->NumRows() != in.NumRows() || act_out->NumCols() != output_dim_) act_out->Resize(in.NumRows(), output_dim_, kUndefined);
     aslp_gemm_epilogue ep = aslp_gemm_epilogue();
     ep.bias = bias_.Data();
-    ep.act_out = sigmoid_out->Data(); ep.ld_act = sigmoid_out->Stride(); ep.act = 1;
+    ep.act_out = act_out->Data(); ep.ld_act = act_out->Stride(); ep.act = act;
     const PlaneSet *pa = nullptr, *pb = nullptr;
     ForwardPlanes(in, &pa, &pb);
     PlaneSet *ap = (act_planes && pa && pb) ? &act_planes->get() : nullptr;
-    if (ap && ap->Reserve(in.NumRows(), output_dim_) && ap->SetBound(1.0f)) {
+    const bool bounded = act != 3;
+    if (ap && bounded && ap->Reserve(in.NumRows(), output_dim_) && ap->SetBound(1.0f)) {
       aslp_planes_as_output(reinterpret_cast<const aslp_planes *>(ap), &ep.planes);
       ep.planes_of = 2;
+    } else if (ap && !bounded && gemm_split16_max_parts(in.NumRows(), output_dim_) <= kS16MaxParts && ap->ReserveParts()) {
+      ep.amax_parts = ap->Parts();
     } else {
       ap = nullptr;
     }
     out->AddMatMat(1.0, in, kNoTrans, linearity_, kTrans, 0.0, &ep, pa, pb);
-    if (ap && aslp_gemm_last_parts() > 0) ap->Tag(sigmoid_out->Data(), sigmoid_out->Stride(), s16_epochs().fwd);   // (the split-fp16 kernel ran)
+    const int left = ap ? aslp_gemm_last_parts() : 0;   // (> 0: the split-fp16 kernel ran)
+    if (left > 0 && bounded) ap->Tag(act_out->Data(), act_out->Stride(), s16_epochs().fwd);
+    else if (left > 0) ap->TagParts(act_out->Data(), left, s16_epochs().fwd);
   }
   // Executor peephole (one-shot): a Sigmoid's backward pass reads the next BackpropagateFnc's in-diff and wants the per-workgroup maxima
   // of it (the scale of ITS result's planes follows from them); they are left in `h`'s maxima array, tagged with the in-diff
@@ -439,13 +448,51 @@ class Sigmoid : public Component {
  private:
   PlaneHolder *in_diff_planes_ = nullptr;
 };
+// Tanh and ReLU take the same peephole as Sigmoid::ProduceInDiffPlanes: both derivatives are <= 1, so |in-diff| <= max |od|.  What the two
+// share: the planes `h` as a kernel's output where it holds the maxima of `od` (np > 0), and the tag behind a launch that wrote them.
+struct InDiffPlanesTarget {
+  InDiffPlanesTarget(PlaneHolder *h, const CuMatrixBase &od, const CuMatrixBase &id) : h_(h), epoch_(s16_epochs().bwd) {
+    np = h ? h->get().PartsFor(od.Data(), epoch_) : 0;
+    if (np > 0 && h->get().Reserve(id.NumRows(), id.NumCols())) {
+      aslp_planes_as_output(reinterpret_cast<const aslp_planes *>(&h->get()), &po);
+      parts = h->get().Parts();
+    } else {
+      np = 0;
+    }
+  }
+  // `served`: what the _p kernel returned (1: in-diff and planes written, the kernel stored the bound)
+  bool Done(int served, const CuMatrixBase &id) {
+    char err[512];
+    if (aslp_get_last_error(err, sizeof(err))) ASLP_ERR << err;
+    if (!served) return false;
+    h_->get().ForgetHostBound();
+    h_->get().Tag(id.Data(), id.Stride(), epoch_);
+    return true;
+  }
+  int np = 0;
+  const float *parts = nullptr;
+  aslp_planes_out po = aslp_planes_out();
+
+ private:
+  PlaneHolder *h_;
+  long epoch_;
+};
 class Tanh : public Component {
  public:
   Tanh(int32 di, int32 dout) : Component(di, dout) {}
-  Component *Copy() const { return new Tanh(*this); }
+  Component *Copy() const { Tanh *c = new Tanh(*this); c->in_diff_planes_ = nullptr; return c; }
   ComponentType GetType() const { return kTanh; }
   void PropagateFnc(const CuMatrixBase &in, CuMatrixBase *out) { out->Tanh(in); }
-  void BackpropagateFnc(const CuMatrixBase &, const CuMatrixBase &out, const CuMatrixBase &od, CuMatrixBase *id) { id->DiffTanh(out, od); }
+  void ProduceInDiffPlanes(PlaneHolder *h) { in_diff_planes_ = h; }   // (one-shot, as Sigmoid's)
+  void BackpropagateFnc(const CuMatrixBase &, const CuMatrixBase &out, const CuMatrixBase &od, CuMatrixBase *id) {
+    InDiffPlanesTarget t(in_diff_planes_, od, *id);
+    in_diff_planes_ = nullptr;
+    if (t.np > 0 && t.Done(aslp_diff_tanh_p(id->Data(), od.Data(), out.Data(), id->Dim(), od.Stride(), out.Stride(), t.parts, t.np, &t.po), *id)) return;
+    id->DiffTanh(out, od);
+  }
+
+ private:
+  PlaneHolder *in_diff_planes_ = nullptr;
 };
 class Dropout : public Component {  // nnet-activation.h:203-273
  public:
@@ -501,12 +548,19 @@ class Dropout : public Component {  // nnet-activation.h:203-273
 class ReLU : public Component {  // :281-298
  public:
   ReLU(int32 di, int32 dout) : Component(di, dout) {}
-  Component *Copy() const { return new ReLU(*this); }
+  Component *Copy() const { ReLU *c = new ReLU(*this); c->in_diff_planes_ = nullptr; return c; }
   ComponentType GetType() const { return kReLU; }
   void PropagateFnc(const CuMatrixBase &in, CuMatrixBase *out) { out->CopyFromMat(in); out->ApplyFloor(0.0); }
+  void ProduceInDiffPlanes(PlaneHolder *h) { in_diff_planes_ = h; }   // (one-shot, as Sigmoid's)
   void BackpropagateFnc(const CuMatrixBase &in, const CuMatrixBase &, const CuMatrixBase &od, CuMatrixBase *id) {
+    InDiffPlanesTarget t(in_diff_planes_, od, *id);
+    in_diff_planes_ = nullptr;
+    if (t.np > 0 && t.Done(aslp_diff_relu_p(id->Data(), in.Data(), od.Data(), id->Dim(), in.Stride(), od.Stride(), t.parts, t.np, &t.po), *id)) return;
     aslp_diff_relu(id->Data(), in.Data(), od.Data(), id->Dim(), in.Stride(), od.Stride());
   }
+
+ private:
+  PlaneHolder *in_diff_planes_ = nullptr;
 };
 
 // ---- Splice / Copy (nnet-various.h:43-330) ----------------------------------------------------------------

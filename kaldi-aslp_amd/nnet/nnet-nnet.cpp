@@ -52,12 +52,27 @@ int32 Nnet::BatchNormOf(int32 i) const {
   }
   return -1;
 }
+// A/B switch ASLP_FUSE_TANH_RELU=0 (read once): Tanh and ReLU layers keep their own forward launch and their plain backward kernels;
+// the Sigmoid path is not touched by it
+static bool FuseTanhRelu() {
+  static const bool off = getenv("ASLP_FUSE_TANH_RELU") != nullptr && getenv("ASLP_FUSE_TANH_RELU")[0] == '0';
+  return !off;
+}
+// the product epilogue's number of an activation that rides in it (aslp_gemm_epilogue.act), 0: none
+static int EpilogueActivation(Component::ComponentType t) {
+  if (t == Component::kSigmoid) return 1;
+  if (!FuseTanhRelu()) return 0;
+  return t == Component::kTanh ? 2 : t == Component::kReLU ? 3 : 0;
+}
 int32 Nnet::AffineSigmoidOf(int32 i) const {
   if (!fuse_layers_ || !alias_links_ || components_[i]->GetType() != Component::kAffineTransform || num_consumers_[i] != 1) return -1;
   for (int32 j = i + 1; j < NumComponents(); j++) {
     const std::vector<int32> &inp = components_[j]->GetInput();
-    if (inp.size() == 1 && inp[0] == i)
-      return (components_[j]->GetType() == Component::kSigmoid && IsDirectLink(j)) ? j : -1;
+    if (inp.size() == 1 && inp[0] == i) {
+      const int act = EpilogueActivation(components_[j]->GetType());
+      // (a Tanh / ReLU whose output branches out to several consumers keeps its own launch; the Sigmoid's condition is what it was)
+      return (act != 0 && IsDirectLink(j) && (act == 1 || num_consumers_[j] <= 1)) ? j : -1;
+    }
   }
   return -1;
 }
@@ -89,6 +104,7 @@ void Nnet::Propagate(const std::vector<const CuMatrixBase *> &in, std::vector<Cu
   S16EpochScope plane_scope(fwd_epoch_, 0);
   for (size_t i = 0; i < input_.size(); i++) in_view_[input_[i]] = in[i];  // InputLayer reads the caller's matrix
   softmax_folded_ = false;
+  last_fused_activations_ = 0;
   std::vector<char> done(components_.size(), 0);  // Sigmoids already produced by the BatchNormalization in front of them
   for (int32 i = 0; i < (int32)components_.size(); i++) {
     if (done[i]) continue;
@@ -122,11 +138,15 @@ void Nnet::Propagate(const std::vector<const CuMatrixBase *> &in, std::vector<Cu
         dynamic_cast<BatchNormalization *>(components_[bn])->UseInputStats(&bn_stats_buf_[i]);
       }
     }
-    if (as >= 0) {  // AffineTransform + Sigmoid forward in one GEMM; both outputs exist, the backward passes stay separate
-      const int32 ac = AffineConsumerOf(as);   // the layer product that reads the activations gets their fp16 planes from the same epilogue
+    if (as >= 0) {  // AffineTransform + Sigmoid / Tanh / ReLU forward in one GEMM; both outputs exist, the backward passes stay separate
+      // the layer product that reads the activations gets their fp16 planes from the same epilogue (ReLU: the maxima its conversion needs);
+      // a consumer of another kind (a LinearTransform) gets the fused activation and no planes
+      const int32 ac = AffineConsumerOf(as);
       PlaneHolder *ap = (ac >= 0 && gemm_split16_serves(num_frame, components_[ac]->OutputDim(), components_[ac]->InputDim()))
                             ? &dynamic_cast<AffineTransform *>(components_[ac])->InputPlanes() : nullptr;
-      dynamic_cast<AffineTransform *>(components_[i])->PropagateWithSigmoid(*in_view_[i], &output_buf_[i], &output_buf_[as], ap);
+      const int act = EpilogueActivation(components_[as]->GetType());
+      dynamic_cast<AffineTransform *>(components_[i])->PropagateWithActivation(*in_view_[i], &output_buf_[i], &output_buf_[as], act, ap);
+      if (act != 1) last_fused_activations_++;
       out_view_[i] = &output_buf_[i];
       in_view_[as] = &output_buf_[i];
       out_view_[as] = &output_buf_[as];
@@ -335,13 +355,17 @@ void Nnet::Backpropagate(const std::vector<const CuMatrixBase *> &out_diff, std:
         if (fuse_layers_ && alias_links_ && !is_input && direct[i]) {
           const int32 below = components_[i]->GetInput()[0];
           const int32 sig = components_[i]->GetType() == Component::kAffineTransform ? below : i;
-          if (components_[sig]->GetType() == Component::kSigmoid && !folded[sig] && direct[sig]) {
+          // (the same for a Tanh or a ReLU in the Sigmoid's place: their derivatives are bounded by 1)
+          const int sig_act = EpilogueActivation(components_[sig]->GetType());
+          if (sig_act != 0 && !folded[sig] && direct[sig]) {
             const int32 lower = components_[sig]->GetInput()[0];
             if (components_[lower]->GetType() == Component::kAffineTransform) {
               AffineTransform *lo = dynamic_cast<AffineTransform *>(components_[lower]);
               if (gemm_split16_serves(lo->OutputDim(), lo->InputDim(), num_frame)) {
-                if (sig == i) dynamic_cast<Sigmoid *>(components_[i])->ProduceInDiffPlanes(&lo->DiffPlanes());
-                else dynamic_cast<AffineTransform *>(components_[i])->LeaveInDiffMaxima(&lo->DiffPlanes());
+                if (sig != i) dynamic_cast<AffineTransform *>(components_[i])->LeaveInDiffMaxima(&lo->DiffPlanes());
+                else if (sig_act == 1) dynamic_cast<Sigmoid *>(components_[i])->ProduceInDiffPlanes(&lo->DiffPlanes());
+                else if (sig_act == 2) dynamic_cast<Tanh *>(components_[i])->ProduceInDiffPlanes(&lo->DiffPlanes());
+                else dynamic_cast<ReLU *>(components_[i])->ProduceInDiffPlanes(&lo->DiffPlanes());
               }
             }
           }

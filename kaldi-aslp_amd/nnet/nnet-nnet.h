@@ -87,6 +87,9 @@ class Nnet {
   // that component's only consumer) into the BatchNormalization kernels.  Values are identical; the intermediate
   // BN output / Sigmoid in-diff buffers are then not materialised (OutputBuffer() on them throws).
   void SetLayerFusion(bool on) { fuse_layers_ = on; }
+  // How many Tanh / ReLU components took their output from the epilogue of the product in front of them in the latest Propagate (for
+  // tests; A/B switch ASLP_FUSE_TANH_RELU=0 sends these two activations through their own launches)
+  int32 LastFusedActivations() const { return last_fused_activations_; }
   // Engine switch (not in the reference): issue AffineTransform::Update (weight-gradient GEMM with the SGD step in its
   // epilogue) on a side stream, ordered after the component's own Backpropagate, so that it shares the chip with the
   // backward pass of the layers below instead of sitting in its critical path; Backpropagate() returns with the main
@@ -111,8 +114,8 @@ class Nnet {
   bool IsFinalSoftmax(int32 i) const;
   int32 FusedSigmoidOf(int32 i) const;  // index of the Sigmoid folded into BatchNormalization i, or -1
   int32 BatchNormOf(int32 i) const;      // index of the BatchNormalization that is AffineTransform i's only consumer (direct link), or -1
-  int32 AffineSigmoidOf(int32 i) const;
-  int32 AffineConsumerOf(int32 c) const;  // index of the AffineTransform that alone reads component c's output (direct link), or -1  // index of the Sigmoid whose forward pass rides in AffineTransform i's GEMM, or -1
+  int32 AffineSigmoidOf(int32 i) const;   // index of the Sigmoid / Tanh / ReLU whose forward pass rides in AffineTransform i's GEMM, or -1
+  int32 AffineConsumerOf(int32 c) const;  // index of the AffineTransform that alone reads component c's output (direct link), or -1
 
   std::vector<Component *> components_;
   std::vector<int32> input_, output_;
@@ -129,6 +132,7 @@ class Nnet {
   bool fuse_layers_ = true;
   bool overlap_updates_ = true;
   bool fold_softmax_request_ = false, softmax_folded_ = false, diff_in_place_ = false;
+  int32 last_fused_activations_ = 0;
   // weight updates issued on the side stream by the latest Backpropagate and not waited for yet (JoinUpdates(): the main stream waits);
   // the next Propagate joins in front of component first_after_updates_
   // (host_wait: the HOST waits -- for callers that free what the updates touch.)  The marker is an event on the side stream of the thread that

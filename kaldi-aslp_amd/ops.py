@@ -243,6 +243,36 @@ def diff_tanh(eout, y, e):
     lib.cudaF_diff_tanh(D3, D3, ptr(_chk(eout)), ptr(_chk(e)), ptr(_chk(y)), dim(eout), dim(e).stride, dim(y).stride); check_error()
 
 
+def diff_relu(in_diff, x, od):
+    """in_diff = heaviside(x) * od, x the PRE-activation (aslp_diff_relu)"""
+    lib.aslp_diff_relu(ptr(_chk(in_diff)), ptr(_chk(x)), ptr(_chk(od)), dim(in_diff), dim(x).stride, dim(od).stride); check_error()
+
+
+def diff_sigmoid_p(eout, y, e, e_max_parts, planes_out):
+    """diff_sigmoid which also leaves the fp16 planes of eout in planes_out (a _lib.PlanesOut), scaled by max(e_max_parts) / 4; 1 = planes
+    written, 0 = eout alone"""
+    rc = lib.aslp_diff_sigmoid_p(ptr(_chk(eout)), ptr(_chk(e)), ptr(_chk(y)), dim(eout), dim(e).stride, dim(y).stride, ptr(_chk(e_max_parts)),
+                                 e_max_parts.numel(), C.byref(planes_out))
+    check_error()
+    return rc
+
+
+def diff_tanh_p(eout, y, e, e_max_parts, planes_out):
+    """diff_tanh with the planes of eout, scaled by max(e_max_parts); 1 = eout and planes written, 0 = not served, nothing launched"""
+    rc = lib.aslp_diff_tanh_p(ptr(_chk(eout)), ptr(_chk(e)), ptr(_chk(y)), dim(eout), dim(e).stride, dim(y).stride, ptr(_chk(e_max_parts)),
+                              e_max_parts.numel(), C.byref(planes_out))
+    check_error()
+    return rc
+
+
+def diff_relu_p(in_diff, x, od, od_max_parts, planes_out):
+    """diff_relu with the planes of in_diff, scaled by max(od_max_parts); 1 = in_diff and planes written, 0 = not served, nothing launched"""
+    rc = lib.aslp_diff_relu_p(ptr(_chk(in_diff)), ptr(_chk(x)), ptr(_chk(od)), dim(in_diff), dim(x).stride, dim(od).stride, ptr(_chk(od_max_parts)),
+                              od_max_parts.numel(), C.byref(planes_out))
+    check_error()
+    return rc
+
+
 def softmax(y, x):
     lib.cudaF_softmax_reduce(0, 0, ptr(_chk(y)), ptr(_chk(x)), dim(y), dim(x).stride); check_error()
 
