@@ -8,6 +8,7 @@
 #pragma once
 #include <chrono>
 #include <cstdint>
+#include <cstdlib>
 #include <cstring>
 #include <iostream>
 #include <limits>
@@ -54,6 +55,17 @@ extern int g_verbose_level;
   do {                                                                      \
     if (!(cond)) ASLP_ERR << "Assertion failed: (" << #cond << ")";         \
   } while (0)
+
+// A/B switches of the engine (DESIGN.md "A/B switches") are environment variables whose first character decides, or which hold a number.
+// One function per switch keeps the answer in a function-local static -- read once per process -- and every user of the switch calls it.
+inline bool EnvBegins(const char *name, char c) {
+  const char *e = getenv(name);
+  return e != nullptr && e[0] == c;
+}
+inline int EnvInt(const char *name, int if_unset) {
+  const char *e = getenv(name);
+  return e ? atoi(e) : if_unset;
+}
 
 struct Timer {  // base/timer.h
   std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();

@@ -55,7 +55,7 @@ int32 Nnet::BatchNormOf(int32 i) const {
 // A/B switch ASLP_FUSE_TANH_RELU=0 (read once): Tanh and ReLU layers keep their own forward launch and their plain backward kernels;
 // the Sigmoid path is not touched by it
 static bool FuseTanhRelu() {
-  static const bool off = getenv("ASLP_FUSE_TANH_RELU") != nullptr && getenv("ASLP_FUSE_TANH_RELU")[0] == '0';
+  static const bool off = EnvBegins("ASLP_FUSE_TANH_RELU", '0');
   return !off;
 }
 // the product epilogue's number of an activation that rides in it (aslp_gemm_epilogue.act), 0: none
@@ -131,7 +131,7 @@ void Nnet::Propagate(const std::vector<const CuMatrixBase *> &in, std::vector<Cu
     {
       // AffineTransform whose only consumer is a BatchNormalization: the GEMM's epilogue leaves the column statistics of its output
       // (32-row partial sums), and the normalisation then streams that output once instead of reading it for statistics first
-      static const bool stats_off = getenv("ASLP_BN_FROM_STATS") != nullptr && getenv("ASLP_BN_FROM_STATS")[0] == '0';  // A/B switch
+      static const bool stats_off = EnvBegins("ASLP_BN_FROM_STATS", '0');  // A/B switch
       const int32 bn = stats_off ? -1 : BatchNormOf(i);
       if (bn >= 0) {
         dynamic_cast<AffineTransform *>(components_[i])->RequestOutputStats(&bn_stats_buf_[i]);
@@ -283,7 +283,7 @@ void Nnet::Backpropagate(const std::vector<const CuMatrixBase *> &out_diff, std:
   // recurrences (one launch per pass) do not: the weight gradients of the layer above then run on the side stream BESIDE the recurrence
   // below, whose workgroups leave most of every CU idle (measured on cfg3: 3.00 -> 2.88 ms per step; the recurrence itself stretches
   // from 190 to ~300 us while 165 us of GEMMs share its CUs, so a third of the gradient time is hidden).  A/B: ASLP_LSTM_SIDE_GRADS=0.
-  static const bool lstm_side_off = getenv("ASLP_LSTM_SIDE_GRADS") != nullptr && getenv("ASLP_LSTM_SIDE_GRADS")[0] == '0';
+  static const bool lstm_side_off = EnvBegins("ASLP_LSTM_SIDE_GRADS", '0');
   bool recurrent_net = false;
   for (int32 i = 0; i < N; i++) {
     if (components_[i]->LatencyBoundPasses()) overlap_updates = false;
@@ -299,7 +299,7 @@ void Nnet::Backpropagate(const std::vector<const CuMatrixBase *> &out_diff, std:
   int32 lowest_updatable = -1;
   for (int32 i = 0; i < N && lowest_updatable < 0; i++)
     if (components_[i]->IsUpdatable()) lowest_updatable = i;
-  static const bool lowest_on_side = getenv("ASLP_LOWEST_UPDATE_ON_SIDE") != nullptr && getenv("ASLP_LOWEST_UPDATE_ON_SIDE")[0] == '1';  // A/B switch
+  static const bool lowest_on_side = EnvBegins("ASLP_LOWEST_UPDATE_ON_SIDE", '1');  // A/B switch
   if (lowest_on_side) lowest_updatable = -1;
   // How many of the LOWEST updatable components keep their update on the main stream.  The side stream starts late (behind the output layer's
   // in-diff product) with the largest update and every update carries an HBM-bound epilogue that does not shrink with the minibatch, so it
@@ -308,7 +308,7 @@ void Nnet::Backpropagate(const std::vector<const CuMatrixBase *> &out_diff, std:
   // per step at minibatch 256; at minibatch 512 and 1024 one is the better choice (0.547 against 0.552, 0.742 against 0.745 ms; with
   // BatchNormalization at 1024: 0.746 against 0.777), and so it is for nets with fewer than four AffineTransforms and for recurrent nets.
   // A/B: ASLP_UPDATES_ON_MAIN=n.
-  static const int on_main_env = [] { const char *e = getenv("ASLP_UPDATES_ON_MAIN"); return e ? atoi(e) : -1; }();
+  static const int on_main_env = EnvInt("ASLP_UPDATES_ON_MAIN", -1);
   int32 main_below = lowest_updatable;   // updates of updatable components with index <= main_below stay on the main stream
   {
     auto is_affine = [&](int32 i) { return components_[i]->GetType() == Component::kAffineTransform && components_[i]->IsUpdatable(); };
@@ -406,7 +406,7 @@ void Nnet::Backpropagate(const std::vector<const CuMatrixBase *> &out_diff, std:
   // component itself) runs beside the last updates instead of behind them -- the input copy, its conversion and the lowest layer's product,
   // 34 of the 40 us for which the main stream used to sit idle at the end of a cfg2 step.  Every other way to the parameters (the
   // accessors below, the C API, aslp_params_changed() of the sync workers) joins first.  A/B: ASLP_LATE_JOIN=0.
-  static const bool late_join_off = getenv("ASLP_LATE_JOIN") != nullptr && getenv("ASLP_LATE_JOIN")[0] == '0';
+  static const bool late_join_off = EnvBegins("ASLP_LATE_JOIN", '0');
   first_after_updates_ = 0;
   if (params_out_silently_ && !silent_writer_logged_) {
     silent_writer_logged_ = true;

@@ -51,14 +51,11 @@ class RecurrentBase : public UpdatableComponent {
   // BackpropagateFnc of a folding subclass: true once per hint, and the following Update() then returns at once
   bool TakeFoldHint() { if (!fold_update_) return false; fold_update_ = false; update_done_ = true; return true; }
   bool SkipFoldedUpdate() { if (!update_done_) return false; update_done_ = false; return true; }
-
- private:
-  bool fold_update_ = false, update_done_ = false;
- protected:
   bool TakeInDiffUnused() { const bool v = in_diff_unused_; in_diff_unused_ = false; return v; }
   bool TakeGradsAside() { const bool v = grads_aside_; grads_aside_ = false; return v; }
+
  private:
-  bool in_diff_unused_ = false, grads_aside_ = false;
+  bool fold_update_ = false, update_done_ = false, in_diff_unused_ = false, grads_aside_ = false;
 };
 
 // fp16 planes (csrc/split16.h) of W_eff and W_eff^T for the split-fp16 products of the per-timestep path (aslp_lstm_step_split16): made
@@ -67,13 +64,17 @@ struct LstmStepPlanes {
   PlaneSet eff, eff_t;
   bool eff_ok = false, eff_t_ok = false;
 };
-struct LstmStepPlanesHolder {   // a copied direction starts without planes
-  LstmStepPlanesHolder() = default;
-  LstmStepPlanesHolder(const LstmStepPlanesHolder &) {}
-  LstmStepPlanesHolder &operator=(const LstmStepPlanesHolder &) { return *this; }
-  LstmStepPlanes *get() { if (!p) p.reset(new LstmStepPlanes()); return p.get(); }
+// A layer's or direction's set of planes: made on first use, and a copied owner starts without
+template <class Planes>
+struct PlanesHolder {
+  PlanesHolder() = default;
+  PlanesHolder(const PlanesHolder &) {}
+  PlanesHolder &operator=(const PlanesHolder &) { return *this; }
+  Planes *get() { if (!p) p.reset(new Planes()); return p.get(); }
+  std::unique_ptr<Planes> p;
+};
+struct LstmStepPlanesHolder : PlanesHolder<LstmStepPlanes> {
   void Invalidate(bool eff, bool eff_t) { if (p) { if (eff) p->eff_ok = false; if (eff_t) p->eff_t_ok = false; } }
-  std::unique_ptr<LstmStepPlanes> p;
 };
 
 struct LstmDir {
@@ -121,13 +122,13 @@ struct LstmDir {
              const aslp_lstm_seq *seq = nullptr, int dir = 0);
   void VecGrads(int T, int S, bool reverse, const CuMatrix &buf, const CuMatrix &dbuf, float mmt, float clip, float lr_fold, const aslp_lstm_seq *seq, int dir);
   void Update(float lr);
-  int VecGradJobs(int S, bool reverse, const CuMatrix &buf, const CuMatrix &dbuf, aslp_rnn_vec_grad *jobs);
+  int VecGradJobs(int S, bool reverse, const CuMatrix &buf, const CuMatrix &dbuf, aslp_rnn_vec_grad *jobs);   // bias + peephole gradient jobs (<= 4)
   double ParamSum() const {   // on the device (Nnet::Check)
     double s = w_x.Sum() + w_r.Sum() + (double)bias.Sum() + (double)peep_f.Sum() + (double)peep_o.Sum();
     if (!cifg) s += (double)peep_i.Sum();
     if (R > 0) s += w_rm.Sum();
     return s;
-  }  // bias + peephole gradient jobs (<= 4)
+  }
 
   // ---- fused-step path: the per-timestep loop lives in LstmFamily (all directions share a launch) ----
   bool FusedOk() const;  // C % 4 == 0 (16-byte operand loads) and not disabled by ASLP_LSTM_UNFUSED=1 (A/B switch for tests)
@@ -136,32 +137,18 @@ struct LstmDir {
   // planes of Weff() (transposed = false) or w_eff_t (true) of n <= 2 directions, whose fp32 matrices are up to date: one conversion for
   // those that are stale.  false: not made (the caller keeps the fp32-instruction kernels)
   static bool RefreshStepPlanes(const LstmDir *const *dirs, int n, bool transposed);
-  // Both directions of a bidirectional layer: every batched product below exists twice with the same shape, and most of them
-  // (K or N = R, or a [R x C] output) cannot fill the chip alone -- they go out as pairs, one launch each (AddMatMatPair).
-  // `with_gemm = false` on the single-direction methods leaves out the product the *Pair function then issues for both.
-  static void RefreshEffPair(const LstmDir &f, const LstmDir &b, const struct S16View *views = nullptr);   // views: planes of w_r (f, b), w_rm (f, b)
-  // pl (may be NULL): where the layer keeps the fp16 planes of these products' operands (LstmPlanes below)
-  static void ForwardPreparePair(const LstmDir &f, const LstmDir &b, const CuMatrixBase &in, int T, int S, const CuMatrixBase *init_f,
-                                 CuMatrix *fbuf, CuMatrix *bbuf, bool persistent, struct LstmPlanes *pl = nullptr);
-  static bool ForwardFinishPair(const LstmDir &f, const LstmDir &b, int T, int S, CuMatrix *fbuf, CuMatrix *bbuf, CuMatrixBase *out,
-                                struct LstmPlanes *pl = nullptr);
-  static void BackwardPreparePair(const LstmDir &f, const LstmDir &b, const CuMatrixBase &od_f, const CuMatrixBase &od_b, int T, int S,
-                                  CuMatrix *fdbuf, CuMatrix *bdbuf, bool persistent, struct LstmPlanes *pl = nullptr);
-  // with_dr = false: d_r (which only the W_rm gradient reads) is left to BackwardDrPair -- the caller issues that with the gradients, beside
-  // the recurrence of the layer below, instead of in front of this layer's in-diff on the main stream.  Returns true if d_r was left out.
-  static bool BackwardFinishPair(const LstmDir &f, const LstmDir &b, const CuMatrixBase &od_f, const CuMatrixBase &od_b, int T, int S,
-                                 CuMatrix *fdbuf, CuMatrix *bdbuf, CuMatrixBase *in_diff, struct LstmPlanes *pl = nullptr, bool with_dr = true);
-  static void BackwardDrPair(const LstmDir &f, const LstmDir &b, const CuMatrixBase &od_f, const CuMatrixBase &od_b, int T, int S,
-                             CuMatrix *fdbuf, CuMatrix *bdbuf, struct LstmPlanes *pl);
-  static void GradsPair(LstmDir &f, LstmDir &b, const CuMatrixBase &in, int T, int S, const CuMatrix &fbuf, const CuMatrix &bbuf,
-                        const CuMatrix &fdbuf, const CuMatrix &bdbuf, float mmt, float clip, float lr_fold, const aslp_lstm_seq *seq = nullptr,
-                        struct LstmPlanes *pl = nullptr);
   const CuMatrixBase &Weff() const { return R > 0 ? static_cast<const CuMatrixBase &>(w_eff) : w_r; }
-  void ForwardPrepare(const CuMatrixBase &in, int T, int S, bool reverse, const CuMatrixBase *init_state, CuMatrix *buf, bool persistent,
-                      bool with_gemm = true) const;
+  // what the per-timestep kernels multiply with: Weff() forward, w_eff_t (transposed) backward
+  const CuMatrixBase &StepWeights(bool transposed) const { return transposed ? static_cast<const CuMatrixBase &>(w_eff_t) : Weff(); }
+  // The buffer half of a pass' preparation -- resize, "not yet published" fill (persistent) or zero, carried state -- and the whole of it:
+  // the buffer, then the batched product in front of the recurrence (forward: x -> gates with the bias; backward: the loss's share of d_m).
+  // The two directions of a bidirectional layer issue that product as a pair (LstmPair below) and call the buffer half alone.
+  void ForwardBufferPrepare(int T, int S, bool reverse, const CuMatrixBase *init_state, CuMatrix *buf, bool persistent) const;
+  void ForwardPrepare(const CuMatrixBase &in, int T, int S, bool reverse, const CuMatrixBase *init_state, CuMatrix *buf, bool persistent) const;
   // returns true if the projected output r(1..T) was also stored at out[:, out_col ...] (only with a projection)
   bool ForwardFinish(int T, int S, CuMatrix *buf, CuMatrixBase *out, int out_col) const;                                   // batched projection
-  void BackwardPrepare(const CuMatrixBase &out_diff, int T, int S, CuMatrix *dbuf, bool persistent, bool with_gemm = true) const;  // dm_ext
+  void BackwardBufferPrepare(int T, int S, CuMatrix *dbuf, bool persistent) const;
+  void BackwardPrepare(const CuMatrixBase &out_diff, int T, int S, CuMatrix *dbuf, bool persistent) const;  // dm_ext
   // with_dr: also form d_r (needed by the W_rm gradient); in_diff == NULL: only that
   void BackwardFinish(const CuMatrixBase &out_diff, int T, int S, bool reverse, CuMatrix *dbuf, CuMatrixBase *in_diff, float beta, bool with_dr) const;
 };
@@ -175,12 +162,27 @@ struct LstmPlanes {
   const float *dg_parts[2] = {nullptr, nullptr};   // per-workgroup maxima of the gate diffs left by this pass' persistent backward launch
   int dg_nparts = 0;
 };
-struct LstmPlanesHolder {   // a copied component starts without planes
-  LstmPlanesHolder() = default;
-  LstmPlanesHolder(const LstmPlanesHolder &) {}
-  LstmPlanesHolder &operator=(const LstmPlanesHolder &) { return *this; }
-  LstmPlanes *get() { if (!p) p.reset(new LstmPlanes()); return p.get(); }
-  std::unique_ptr<LstmPlanes> p;
+
+// Both directions of a bidirectional layer: every batched product of a pass exists twice with the same shape, and most of them
+// (K or N = R, or a [R x C] output) cannot fill the chip alone -- they go out as pairs, one launch each (AddMatMatPair), from the fp16
+// planes of their operands where the layer has them.  What those functions work on, as a bundle of references that LstmFamily builds
+// once per pass: the directions, their activation and diff buffers [(T+2)S x Width], and where the layer keeps the planes.
+// Directions of different shape (or ASLP_LSTM_PAIR=0) fall back to the single-direction methods of LstmDir.
+struct LstmPair {
+  LstmDir &f, &b;
+  CuMatrix &fbuf, &bbuf, &fdbuf, &bdbuf;
+  int T, S;
+  LstmPlanes &pl;
+
+  void RefreshEff(const S16View *views = nullptr) const;   // views: planes of w_r (f, b), w_rm (f, b)
+  void ForwardPrepare(const CuMatrixBase &in, const CuMatrixBase *init_f, bool persistent) const;
+  bool ForwardFinish(CuMatrixBase *out) const;
+  void BackwardPrepare(const CuMatrixBase &od_f, const CuMatrixBase &od_b, bool persistent) const;
+  // with_dr = false: d_r (which only the W_rm gradient reads) is left to BackwardDr -- the caller issues that with the gradients, beside
+  // the recurrence of the layer below, instead of in front of this layer's in-diff on the main stream.  Returns true if d_r was left out.
+  bool BackwardFinish(const CuMatrixBase &od_f, const CuMatrixBase &od_b, CuMatrixBase *in_diff, bool with_dr) const;
+  void BackwardDr(const CuMatrixBase &od_f, const CuMatrixBase &od_b) const;
+  void Grads(const CuMatrixBase &in, float mmt, float clip, float lr_fold, const aslp_lstm_seq *seq) const;
 };
 
 // Shared implementation; the concrete classes below only fix the configuration.
@@ -221,6 +223,20 @@ class LstmFamily : public RecurrentBase {
   const CuMatrix &ForwardBuffer(int dir) const { return dir == 0 ? f_buf_ : b_buf_; }
 
  protected:
+  // The recurrence of one pass: the persistent kernel's descriptor (geometry first, pointers once the buffers exist), its stream windows,
+  // and whether that kernel takes the pass at all (else: one launch per timestep)
+  struct SeqPlan { aslp_lstm_seq q; int per_launch, nwin; bool persistent; };
+  SeqPlan ChoosePath(int T, int S, int pass) const;
+  bool Carried() const { return !cfg_.bidir || cfg_.lc; }   // the forward-in-time direction starts from the previous batch's state
+  bool CarriedStateProduct(int S, bool persistent);
+  void ForwardPersistent(SeqPlan *plan, bool first_in_kernel);
+  void ForwardPerTimestep(int T, int S);
+  void BackwardPersistent(SeqPlan *plan);
+  void BackwardPerTimestep(int T, int S);
+  aslp_lstm_step StepDescriptor(int S, int ld, bool transposed) const;
+  bool StepPlanes(int ndir, bool transposed, aslp_lstm_step_h *ah) const;
+  LstmPair Pair(int T, int S) { return LstmPair{f_, b_, f_buf_, b_buf_, f_dbuf_, b_dbuf_, T, S, *planes_.get()}; }
+
   Config cfg_;
   int32 ncell_, nrecur_, nstream_, chunk_size_;
   BaseFloat clip_gradient_;
@@ -230,7 +246,7 @@ class LstmFamily : public RecurrentBase {
   std::vector<int32> sequence_lengths_; // BLstm* masking
   CuArray<int32> seq_len_dev_;
   CuMatrix f_buf_, b_buf_, f_dbuf_, b_dbuf_;
-  LstmPlanesHolder planes_;   // made on first use
+  PlanesHolder<LstmPlanes> planes_;   // made on first use
   bool last_persistent_ = false;   // the last Propagate ran the recurrence as ONE persistent launch (else: launches per timestep)
   CuMatrix grad_partial_;          // per-chain bias / peephole gradient sums of the persistent backward launch (aslp_lstm_seq.grad_partial)
   CuVector dmax_parts_;            // 2 x 256 per-workgroup maxima of the gate diffs from the same launch (aslp_lstm_seq.dmax_parts)
@@ -258,13 +274,6 @@ ASLP_LSTM_CLASS(LstmCifgProjectedStreams, kLstmCifgProjectedStreams, false, true
 // path (aslp_gru_step_pieces): re-made at the top of every pass that reads them, so there is no validity to track
 struct GruStepPlanes {
   PlaneSet zr, mg, zr_t, mg_t;
-};
-struct GruStepPlanesHolder {   // a copied component starts without planes
-  GruStepPlanesHolder() = default;
-  GruStepPlanesHolder(const GruStepPlanesHolder &) {}
-  GruStepPlanesHolder &operator=(const GruStepPlanesHolder &) { return *this; }
-  GruStepPlanes *get() { if (!p) p.reset(new GruStepPlanes()); return p.get(); }
-  std::unique_ptr<GruStepPlanes> p;
 };
 
 // GruStreams (nnet-gru-streams.h:39-482)
@@ -297,7 +306,7 @@ class GruStreams : public RecurrentBase {
   CuVector bias_, bias_corr_;
   CuMatrix buf_, dbuf_;
   CuMatrix w_zr_h_t_, w_m_g_t_;  // transposed recurrent matrices for the fused backward step
-  GruStepPlanesHolder step_planes_;
+  PlanesHolder<GruStepPlanes> step_planes_;
 };
 
 }  // namespace aslp

@@ -144,3 +144,24 @@ def test_lstm_layer_products_from_prepared_planes(tmp_path):
     # the buffers' preparation for the persistent kernels as a launch of its own instead of riding along with the conversion launch behind it
     # (split16.h SeqFillJob): the same stores, the same bits
     assert np.array_equal(run(tmp_path, "fill_alone", ASLP_LSTM_FILL_ALONG="0", **shape), default)
+
+
+_planes_shape_default = []   # the default run at the shape of the test above, made once for the cases below
+
+
+@pytest.mark.parametrize("switch", ["ASLP_LSTM_PAIR", "ASLP_LSTM_VEC_FUSED"])
+def test_pair_and_fused_vector_gradient_switches_agree_with_the_default(tmp_path, switch):
+    """ASLP_LSTM_PAIR=0: every batched product of the two directions as two launches of the single-direction kernels instead of one pair
+    launch (from operands converted call by call instead of the layer's prepared planes).  ASLP_LSTM_VEC_FUSED=0: the bias and peephole
+    gradients by a pass over the diff buffers instead of from the sums the persistent backward launch leaves per chain.  Both change the order
+    of some sums and nothing else: same values to fp32 rounding, at the shape at which the planes path is live (the bar of
+    test_lstm_layer_products_from_prepared_planes)."""
+    shape = {"AB_S": "32", "AB_CHUNK": "5", "AB_T": "8", "AB_D": "64"}
+    if not _planes_shape_default:
+        _planes_shape_default.append(run(tmp_path, "default", **shape))
+    default = _planes_shape_default[0]
+    assert np.isfinite(default).all()
+    other = run(tmp_path, "off", **dict(shape, **{switch: "0"}))
+    rel, big = np.linalg.norm(other - default) / np.linalg.norm(default), np.abs(other - default).max() / max(1.0, np.abs(default).max())
+    print("%s=0 against the default: relative %.2e, largest element %.2e" % (switch, rel, big))
+    assert rel < 1e-5 and big < 1e-4, (switch, rel, big)
