@@ -275,6 +275,21 @@ _sig("aslp_diff_sigmoid_p", _i, _vp, _vp, _vp, _md, _i, _i, _vp, _i, C.POINTER(P
 _sig("aslp_diff_relu_p", _i, _vp, _vp, _vp, _md, _i, _i, _vp, _i, C.POINTER(PlanesOut))
 _sig("aslp_diff_tanh_p", _i, _vp, _vp, _vp, _md, _i, _i, _vp, _i, C.POINTER(PlanesOut))
 _sig("aslp_max_norm_rows", None, _vp, _md, _f)
+# front-end components (csrc/conv_pool.hip)
+_sig("aslp_conv_gather_patches", None, _vp, _i, _vp, _md, _i, _i, _i, _i, _i)
+_sig("aslp_conv_in_diff", None, _vp, _md, _vp, _i, _i, _i, _i, _i, _i)
+_sig("aslp_max_pool_forward", None, _vp, _i, _vp, _md, _i, _i, _i)
+_sig("aslp_max_pool_backward", None, _vp, _i, _vp, _md, _vp, _i, _vp, _i, _i, _i, _i)
+_sig("aslp_length_norm_forward", None, _vp, _i, _vp, _md, _vp)
+_sig("aslp_group_pnorm_backward", None, _vp, _i, _vp, _md, _vp, _i, _vp, _i, _i, _f)
+_sig("aslp_group_max_backward", None, _vp, _i, _vp, _md, _vp, _i, _vp, _i, _i)
+_sig("cudaF_max", None, _d3, _d3, _vp, _vp, _md, _i)
+_sig("cudaF_equal_element_mask", None, _d3, _d3, _vp, _vp, _vp, _md, _i, _i)
+_sig("cudaF_group_pnorm", None, _d3, _d3, _vp, _vp, _md, _i, _i, _f)
+_sig("cudaF_calc_pnorm_deriv", None, _d3, _d3, _vp, _vp, _vp, _md, _i, _i, _f)
+_sig("cudaF_group_max", None, _d3, _d3, _vp, _vp, _md, _i, _i)
+_sig("cudaF_calc_group_max_deriv", None, _d3, _d3, _vp, _vp, _vp, _md, _i, _i)
+_sig("cudaF_mul_rows_group_mat", None, _d3, _d3, _vp, _vp, _md, _i, _i)
 
 
 # CTC (B5, include/aslp_ctc.h)
