@@ -29,6 +29,9 @@ void aslp_device_reset_profile(void);                                       /* C
 int aslp_device_check_gpu_health(void);                                     /* CuDevice::CheckGpuHealth cu-device.h:104 */
 /* "free:...M, used:...M, total:...M, free/total:..." like CuDevice::GetFreeMemory (cu-device.h:93) */
 int aslp_device_get_free_memory(char *buf, int buflen, long long *free_bytes, long long *total_bytes);
+/* How often this process has copied device memory to the host and waited for the stream to do it (every such copy empties the launch queue).
+ * Only ever grows; tests and tools read it before and after a stretch of work that is meant to stay asynchronous. */
+long long aslp_device_to_host_syncs(void);
 
 #ifdef __cplusplus
 }

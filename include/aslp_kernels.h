@@ -767,6 +767,30 @@ void cudaF_compute_ctc_error_multiple_sequence(aslp_dim3 Gr, aslp_dim3 Bl, float
 /* max-norm row shrink (nnet-affine-transform.h:231-243) */
 void aslp_max_norm_rows(float *W, MatrixDim d, float max_norm);
 
+/* ---- multi-stream batches gathered on the device (csrc/stream_batch.hip; no reference counterpart: the reference assembles them on the host) ----
+ * dst is [B*S x D] with row stride ldd; row r belongs to stream r % S and receives row src_frame[r] of that stream's source matrix, or +0.0
+ * in every column where src_frame[r] == -1.  Bit patterns are copied, nothing is computed: NaN payloads and -0.0 survive.  Columns at or
+ * beyond D of dst are not written, and no source row outside [0, rows) is read.  16-byte accesses where D, ldd, every stride and every base
+ * allow (streams with rows == 0 are never read and do not count), 4-byte accesses otherwise.
+ * The table and the plan are given twice: the HOST copies are validated here before anything is launched (a frame < -1 or >= rows, a stride
+ * < D: the error slot is set, the return value is non-zero and nothing runs), the DEVICE copies are what the kernel reads -- the caller
+ * uploads them, in stream order before this call.  Runs on the calling thread's current stream: a source buffer that is overwritten later
+ * on that stream is ordered behind the gather that reads it. */
+typedef struct {
+  const float *base;   /* device; may be NULL when rows == 0 */
+  int stride;          /* floats */
+  int rows;
+} aslp_stream_src;
+int aslp_gather_stream_rows(float *dst, int ldd, int B, int S, int D, const aslp_stream_src *src_host, const aslp_stream_src *src_dev,
+                            const int32_cuda *src_frame_host, const int32_cuda *src_frame_dev);
+/* 1: these operands take the 16-byte form, 0: the 4-byte form; no launch.  For tests. */
+int aslp_gather_stream_rows_path(const float *dst, int ldd, int S, int D, const aslp_stream_src *src_host);
+/* 1: SequenceDataReader and the chunked stream tools assemble their batches on the host, as before the gather existed (every utterance's
+ * transformed features come back from the device first); 0: on the device; on < 0: what ASLP_STREAM_BATCH_HOST=1 said (read once per
+ * process).  Same batches either way, bit for bit. */
+void aslp_stream_batch_on_host(int on);
+int aslp_stream_batch_on_host_get(void);
+
 #ifdef __cplusplus
 }
 #endif

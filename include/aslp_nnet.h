@@ -151,6 +151,38 @@ int aslp_matrix_randomizer_state(aslp_matrix_randomizer_t r, int state[3]);
 /* Value(): a view of the current minibatch rows inside the cache (valid until the next AddData / Randomize) */
 int aslp_matrix_randomizer_value(aslp_matrix_randomizer_t r, const float **dev, int *rows, int *cols, int *stride);
 
+/* ---- SequenceDataReader (aslp-nnet/data-reader.h:48-100, data-reader.cc:178-340) ----------------------------------
+ * num_stream utterances advance in parallel, batch_size frames per read, batch row t * num_stream + s; the features run targets_delay
+ * frames ahead of the targets (the last frame repeats); an exhausted stream repeats its last frame and target under mask 0 and takes the
+ * next utterance at the next read; with skip_width > 1 a stream trains on the frames skip_offset, skip_offset + skip_width, ... of its
+ * utterance.  `transform` (may be NULL) is applied to every utterance on the device and must outlive the reader.
+ * By default the batch is gathered on the device from utterances that stay there (aslp_gather_stream_rows, include/aslp_kernels.h) and no
+ * read waits for the device; under aslp_stream_batch_on_host(1) / ASLP_STREAM_BATCH_HOST=1 (as it stood when the reader was opened) it is
+ * assembled on the host.  Same batches either way, bit for bit. */
+typedef struct aslp_sequence_reader_s *aslp_sequence_reader_t;
+typedef struct {
+  int batch_size, num_stream, drop_len, skip_width, targets_delay, skip_offset;
+} aslp_sequence_reader_options;
+typedef struct {
+  const float *feat;             /* device [rows x cols], row stride `stride`; as it was when every stream was exhausted before the read */
+  int rows, cols, stride;
+  const int32_t *labels;         /* device [num_labels]: the row's pdf where its target is one-hot (one pair, weight 1), -1 elsewhere */
+  const float *mask;             /* device [num_labels]: 1 where the row counts in the loss */
+  int num_labels;                /* batch_size * num_stream */
+  const int32_t *labels_host;    /* the same two on the host */
+  const float *mask_host;
+  const int32_t *new_utt_flags;  /* host [num_stream]: 1 where the stream took a new utterance for this batch */
+  int num_stream;
+  int one_hot;                   /* no label is -1: labels + mask can go to aslp_xent_eval_batch as they are */
+  int done;                      /* aslp_sequence_reader_done() after this read */
+} aslp_sequence_batch;
+int aslp_sequence_reader_open(const char *feature_rspecifier, const char *targets_rspecifier, const aslp_sequence_reader_options *opts,
+                              aslp_nnet_t transform, aslp_sequence_reader_t *out);
+/* SequenceDataReader::ReadData.  num_pdf: a label >= num_pdf is an error.  The pointers in *out stay valid until the next call on r. */
+int aslp_sequence_reader_read(aslp_sequence_reader_t r, int num_pdf, aslp_sequence_batch *out);
+int aslp_sequence_reader_done(aslp_sequence_reader_t r);   /* 1 / 0; < 0 on error */
+void aslp_sequence_reader_free(aslp_sequence_reader_t r);
+
 #ifdef __cplusplus
 }
 #endif

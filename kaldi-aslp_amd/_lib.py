@@ -87,6 +87,11 @@ class SodSolver(C.Structure):
                 ("beta2", C.c_float), ("corr1", C.c_float), ("corr2", C.c_float)]
 
 
+class StreamSrc(C.Structure):
+    """aslp_stream_src (include/aslp_kernels.h)"""
+    _fields_ = [("base", C.c_void_p), ("stride", C.c_int), ("rows", C.c_int)]
+
+
 class CtcComputeInfo(C.Structure):
     """warp-ctc/include/ctc.h:45-60 (ctcComputeInfo: loc + union{num_threads, stream})"""
     _fields_ = [("loc", C.c_int), ("stream_or_threads", C.c_void_p)]
@@ -290,6 +295,12 @@ _sig("cudaF_calc_pnorm_deriv", None, _d3, _d3, _vp, _vp, _vp, _md, _i, _i, _f)
 _sig("cudaF_group_max", None, _d3, _d3, _vp, _vp, _md, _i, _i)
 _sig("cudaF_calc_group_max_deriv", None, _d3, _d3, _vp, _vp, _vp, _md, _i, _i)
 _sig("cudaF_mul_rows_group_mat", None, _d3, _d3, _vp, _vp, _md, _i, _i)
+# multi-stream batches gathered on the device (csrc/stream_batch.hip)
+_sig("aslp_gather_stream_rows", _i, _vp, _i, _i, _i, _i, C.POINTER(StreamSrc), _vp, C.POINTER(C.c_int32), _vp)
+_sig("aslp_gather_stream_rows_path", _i, _vp, _i, _i, _i, C.POINTER(StreamSrc))
+_sig("aslp_stream_batch_on_host", None, _i)
+_sig("aslp_stream_batch_on_host_get", _i)
+_sig("aslp_device_to_host_syncs", C.c_longlong)
 
 
 # CTC (B5, include/aslp_ctc.h)

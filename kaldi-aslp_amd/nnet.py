@@ -183,6 +183,71 @@ def _i32arr(v):
     return (C.c_int32 * max(1, len(v)))(*[int(x) for x in v])
 
 
+class SequenceReaderOptions(C.Structure):
+    """aslp_sequence_reader_options (include/aslp_nnet.h)"""
+    _fields_ = [("batch_size", _i), ("num_stream", _i), ("drop_len", _i), ("skip_width", _i), ("targets_delay", _i), ("skip_offset", _i)]
+
+
+class SequenceBatch(C.Structure):
+    """aslp_sequence_batch (include/aslp_nnet.h)"""
+    _fields_ = [("feat", _vp), ("rows", _i), ("cols", _i), ("stride", _i), ("labels", _vp), ("mask", _vp), ("num_labels", _i),
+                ("labels_host", _i32p), ("mask_host", C.POINTER(_f)), ("new_utt_flags", _i32p), ("num_stream", _i), ("one_hot", _i), ("done", _i)]
+
+
+_sig("aslp_sequence_reader_open", _i, C.c_char_p, C.c_char_p, C.POINTER(SequenceReaderOptions), _H, C.POINTER(_H))
+_sig("aslp_sequence_reader_read", _i, _H, _i, C.POINTER(SequenceBatch))
+_sig("aslp_sequence_reader_done", _i, _H)
+_sig("aslp_sequence_reader_free", None, _H)
+
+
+class SequenceReader:
+    """SequenceDataReader (aslp-nnet/data-reader.h:48-100) over two Kaldi tables: num_stream utterances side by side, batch_size frames per
+    read, row t * num_stream + s.  `transform` (an Nnet, optional) is applied to every utterance on the device.  The batches are gathered on
+    the device unless ops.stream_batch_on_host(1) / ASLP_STREAM_BATCH_HOST=1 was in force when the reader was opened."""
+
+    def __init__(self, feature_rspecifier, targets_rspecifier, batch_size=20, num_stream=4, targets_delay=0, skip_width=1, skip_offset=0,
+                 drop_len=0, transform=None):
+        self.h = _H()
+        self.transform = transform   # must outlive the reader
+        o = SequenceReaderOptions(int(batch_size), int(num_stream), int(drop_len), int(skip_width), int(targets_delay), int(skip_offset))
+        _ok(lib.aslp_sequence_reader_open(str(feature_rspecifier).encode(), str(targets_rspecifier).encode(), C.byref(o),
+                                          transform.h if transform is not None else None, C.byref(self.h)))
+
+    def __del__(self):
+        if getattr(self, "h", None) and lib is not None:
+            lib.aslp_sequence_reader_free(self.h)
+            self.h = None
+
+    def Done(self):
+        rc = lib.aslp_sequence_reader_done(self.h)
+        if rc < 0:
+            raise RuntimeError(lib.aslp_nnet_last_error().decode())
+        return bool(rc)
+
+    def Read(self, num_pdf=1 << 30):
+        """one batch: dict(feat=[rows x cols] float32, labels=[n] int32 (-1: the row's target is not one-hot), mask=[n] float32 -- device
+        tensors, copies of the reader's buffers --, labels_host / mask_host / new_utt_flags as numpy arrays, one_hot, done)"""
+        import numpy as np
+        from ._lib import MatrixDim
+        b = SequenceBatch()
+        _ok(lib.aslp_sequence_reader_read(self.h, int(num_pdf), C.byref(b)))
+        n = b.num_labels
+        feat = torch.empty(b.rows, b.cols, device="cuda")
+        labels = torch.empty(n, dtype=torch.int32, device="cuda")
+        mask = torch.empty(n, device="cuda")
+        if b.rows and b.cols:
+            lib.aslp_copy_mat(ptr(feat), MatrixDim(b.rows, b.cols, b.cols), b.feat, b.stride)
+        if n:   # (bit patterns: the copy kernel computes nothing)
+            lib.aslp_copy_mat(ptr(labels), MatrixDim(1, n, n), b.labels, n)
+            lib.aslp_copy_mat(ptr(mask), MatrixDim(1, n, n), b.mask, n)
+        check_error()
+        return dict(feat=feat, labels=labels, mask=mask,
+                    labels_host=np.ctypeslib.as_array(b.labels_host, shape=(n,)).copy() if n else np.zeros(0, np.int32),
+                    mask_host=np.ctypeslib.as_array(b.mask_host, shape=(n,)).copy() if n else np.zeros(0, np.float32),
+                    new_utt_flags=np.ctypeslib.as_array(b.new_utt_flags, shape=(b.num_stream,)).copy(),
+                    one_hot=bool(b.one_hot), done=bool(b.done))
+
+
 def _flat(labels):
     flat = [int(x) for l in labels for x in l]
     return _i32arr(flat), _i32arr([len(l) for l in labels])

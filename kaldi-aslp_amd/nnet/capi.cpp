@@ -7,6 +7,7 @@
 
 #include "aslp_nnet.h"
 #include "ctc-loss.h"
+#include "data-reader.h"
 #include "nnet-loss.h"
 #include "nnet-nnet.h"
 #include "nnet-randomizer.h"
@@ -39,6 +40,16 @@ struct aslp_eesenctc_s {
 struct aslp_warpctc_s {
   WarpCtc ctc;
   CuMatrix diff;
+};
+struct aslp_sequence_reader_s {
+  aslp_sequence_reader_s(const char *feats, const char *targets, const SequenceDataReaderOptions &o) : reader(feats, targets, o) {}
+  SequenceDataReader reader;
+  CuMatrix feat;
+  Posterior target;
+  std::vector<BaseFloat> mask_host;
+  std::vector<int32> labels_host, flags;
+  CuArray<int32> labels;
+  CuVector mask;
 };
 static void SplitLabels(const int32_t *flat, const int32_t *lens, int n, std::vector<std::vector<int32>> *out) {
   out->resize(n);
@@ -402,6 +413,61 @@ int aslp_matrix_randomizer_value(aslp_matrix_randomizer_t r, const float **dev, 
   API_BEGIN
   const CuMatrixBase &m = r->r.Value();
   *dev = m.Data(); *rows = m.NumRows(); *cols = m.NumCols(); *stride = m.Stride();
+  API_END
+}
+
+// ---- SequenceDataReader (data-reader.h) ----------------------------------------------------------------------------
+int aslp_sequence_reader_open(const char *feature_rspecifier, const char *targets_rspecifier, const aslp_sequence_reader_options *opts,
+                              aslp_nnet_t transform, aslp_sequence_reader_t *out) {
+  API_BEGIN
+  if (!feature_rspecifier || !targets_rspecifier || !opts || !out) ASLP_ERR << "aslp_sequence_reader_open: null argument";
+  if (opts->batch_size <= 0 || opts->num_stream <= 0 || opts->targets_delay < 0 || opts->skip_offset < 0 ||
+      (opts->skip_width > 1 ? opts->skip_offset >= opts->skip_width : opts->skip_offset != 0))
+    ASLP_ERR << "aslp_sequence_reader_open: bad options";
+  SequenceDataReaderOptions o;
+  o.batch_size = opts->batch_size;
+  o.num_stream = opts->num_stream;
+  o.drop_len = opts->drop_len;
+  o.skip_width = opts->skip_width;
+  o.targets_delay = opts->targets_delay;
+  aslp_sequence_reader_s *h = new aslp_sequence_reader_s(feature_rspecifier, targets_rspecifier, o);
+  h->reader.SetSkipOffset(opts->skip_offset);
+  if (transform) h->reader.SetFeatureTransform(&transform->nnet);
+  *out = h;
+  API_END
+}
+void aslp_sequence_reader_free(aslp_sequence_reader_t r) { delete r; }
+int aslp_sequence_reader_done(aslp_sequence_reader_t r) {
+  try { return r->reader.Done() ? 1 : 0; } catch (const std::exception &e) { t_err = e.what(); return -1; }
+}
+int aslp_sequence_reader_read(aslp_sequence_reader_t r, int num_pdf, aslp_sequence_batch *out) {
+  API_BEGIN
+  if (!r || !out) ASLP_ERR << "aslp_sequence_reader_read: null argument";
+  if (r->reader.ReadData(&r->feat, &r->target, &r->mask_host, num_pdf, &r->labels, &r->mask)) {
+    r->labels_host = r->reader.BatchLabelsHost();
+  } else {  // soft targets, rows without a target, or the host assembly: the labels of the one-hot rows, from the Posterior
+    r->labels_host.resize(r->target.size());
+    for (size_t i = 0; i < r->target.size(); i++) r->labels_host[i] = StreamBatcher::OneHotLabel(r->target[i]);
+    r->labels = r->labels_host;
+    HostVector hv;
+    hv.data = r->mask_host;
+    r->mask = hv;
+  }
+  r->flags = r->reader.GetNewUttFlags();
+  out->feat = r->feat.Data();
+  out->rows = r->feat.NumRows();
+  out->cols = r->feat.NumCols();
+  out->stride = r->feat.Stride();
+  out->labels = r->labels.Data();
+  out->mask = r->mask.Data();
+  out->num_labels = (int)r->labels_host.size();
+  out->labels_host = r->labels_host.data();
+  out->mask_host = r->mask_host.data();
+  out->new_utt_flags = r->flags.data();
+  out->num_stream = (int)r->flags.size();
+  out->one_hot = 1;
+  for (int32 l : r->labels_host) if (l < 0) out->one_hot = 0;
+  out->done = r->reader.Done() ? 1 : 0;
   API_END
 }
 

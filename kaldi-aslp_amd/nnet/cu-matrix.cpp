@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <cstdlib>
 #include <map>
@@ -100,8 +101,11 @@ void DeviceFree(void *p) {
   g_free.insert({it->second, p});
   g_live.erase(it);
 }
+static std::atomic<long long> g_d2h_syncs{0};
+long long DeviceToHostSyncs() { return g_d2h_syncs.load(); }
 void DeviceToHost(void *dst, const void *src, size_t bytes) {
   if (!bytes) return;
+  g_d2h_syncs.fetch_add(1);
   CheckHip(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, cur_stream()), "hipMemcpy D2H");
   CheckHip(hipStreamSynchronize(cur_stream()), "hipStreamSynchronize");
 }
@@ -451,6 +455,7 @@ void CuMatrixBase::CopyFromPinnedHost(const float *src, int ld) {
 }
 void CuMatrixBase::CopyToHost(float *dst, int ld) const {
   if (!rows_) return;
+  g_d2h_syncs.fetch_add(1);   // (a DeviceToHost with a pitch: the same wait)
   CheckHip(hipMemcpy2DAsync(dst, sizeof(float) * ld, data_, sizeof(float) * stride_, sizeof(float) * cols_, rows_,
                             hipMemcpyDeviceToHost, cur_stream()), "hipMemcpy2D D2H");
   CheckHip(hipStreamSynchronize(cur_stream()), "hipStreamSynchronize");

@@ -21,6 +21,7 @@ enum MatrixTransposeType { kNoTrans = 0, kTrans = 1 };
 void *DeviceAlloc(size_t bytes);
 void DeviceFree(void *p);
 void DeviceToHost(void *dst, const void *src, size_t bytes);
+long long DeviceToHostSyncs();   // DeviceToHost / CuMatrixBase::CopyToHost calls so far, each of which waited for the stream (aslp_device_to_host_syncs)
 void HostToDevice(void *dst, const void *src, size_t bytes);
 void DeviceToDevice(void *dst, const void *src, size_t bytes);
 void DeviceMemset(void *dst, int v, size_t bytes);

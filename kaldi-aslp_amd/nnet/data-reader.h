@@ -14,9 +14,11 @@
 #include "cu-device.h"
 #include "kaldi-table.h"
 #include "nnet-component.h"
+#include "nnet-loss.h"
 #include "nnet-nnet.h"
 #include "nnet-randomizer.h"
 #include "parse-options.h"
+#include "stream-batcher.h"
 
 namespace aslp {
 
@@ -463,7 +465,8 @@ class SequenceDataReader {
   SequenceDataReader(const std::string &feature_rspecifier, const std::string &targets_rspecifier, const SequenceDataReaderOptions &read_opts)
       : feature_reader_(feature_rspecifier), target_reader_(targets_rspecifier), read_opts_(read_opts), read_done_(false),
         keys_(read_opts.num_stream), feats_(read_opts.num_stream), targets_(read_opts.num_stream), curt_(read_opts.num_stream, 0),
-        lent_(read_opts.num_stream, 0), new_utt_flags_(read_opts.num_stream, 0) {}
+        lent_(read_opts.num_stream, 0), new_utt_flags_(read_opts.num_stream, 0), host_batch_(aslp_stream_batch_on_host_get() != 0),
+        batcher_(read_opts.num_stream) {}
   bool Done() { return read_done_ && feature_reader_.Done(); }
   const std::vector<int32> &GetNewUttFlags() const { return new_utt_flags_; }
   // aslp-nnet-train-lstm-streams-skip.cc:160-225: that tool runs skip_width passes over the data, pass k keeping the frames
@@ -477,11 +480,71 @@ class SequenceDataReader {
   void ReadData(CuMatrix *feat, Posterior *target, std::vector<BaseFloat> *frame_mask) {
     ASLP_ASSERT(feat != NULL && target != NULL && frame_mask != NULL);
     if (Done()) ASLP_ERR << "Already read done!";
-    AddNewUtt();
-    FillBatchBuff(feat, target, frame_mask);
+    if (host_batch_) {
+      AddNewUtt();
+      FillBatchBuff(feat, target, frame_mask);
+      return;
+    }
+    AddNewUttOnDevice();
+    GatherBatch(feat, frame_mask);
+    batcher_.BatchTargets(target);
   }
+  // The same batch with its targets as device labels and its mask on the device as well, for Xent::EvalLabels(const CuVectorBase &,
+  // const CuMatrixBase &, const CuArray<int32> &, CuMatrix *) -- the entry that Xent::Eval ends in for a Posterior of one-hot targets, so
+  // the loss and its sums are the same to the bit.  true: *labels and *mask_dev are set and *target was left alone.  false: some row's target is
+  // not one-hot (soft posteriors, a stream that never received an utterance), a label >= num_pdf being the error it is in Xent::Eval, or the
+  // batches are assembled on the host (aslp_stream_batch_on_host); *target is filled then, as by the call above, and goes to Xent::Eval.
+  bool ReadData(CuMatrix *feat, Posterior *target, std::vector<BaseFloat> *frame_mask, int32 num_pdf, CuArray<int32> *labels, CuVector *mask_dev) {
+    ASLP_ASSERT(labels != NULL && mask_dev != NULL);
+    if (host_batch_) { ReadData(feat, target, frame_mask); return false; }
+    ASLP_ASSERT(feat != NULL && target != NULL && frame_mask != NULL);
+    if (Done()) ASLP_ERR << "Already read done!";
+    AddNewUttOnDevice();
+    GatherBatch(feat, frame_mask);
+    // (every stream exhausted: the targets are those of the batch before, like `feat`; only the mask changes)
+    if (!batcher_.BatchLabels(num_pdf, &labels_host_)) { batcher_.BatchTargets(target); return false; }
+    *labels = labels_host_;
+    mask_host_.data = *frame_mask;
+    *mask_dev = mask_host_;
+    return true;
+  }
+  const std::vector<int32> &BatchLabelsHost() const { return labels_host_; }   // what *labels holds after a call that returned true
 
  private:
+  // the device path (stream-batcher.h): the utterance stays where the transform left it, the batch is gathered there
+  void AddNewUttOnDevice() {
+    for (int s = 0; s < read_opts_.num_stream; s++) {
+      if (!batcher_.StreamDone(s)) { new_utt_flags_[s] = 0; continue; }
+      while (!feature_reader_.Done()) {
+        const std::string key = feature_reader_.Key();
+        const HostMatrix &raw = feature_reader_.Value();
+        if (read_opts_.drop_len > 0 && raw.rows > read_opts_.drop_len) { ASLP_WARN << key << ", too long, droped"; feature_reader_.Next(); continue; }
+        if (transform_ != NULL) {
+          dev_in_ = raw;
+          transform_->Feedforward(dev_in_, &dev_out_);
+        }
+        const int32 rows = transform_ != NULL ? dev_out_.NumRows() : raw.rows;
+        if (!target_reader_.HasKey(key)) { ASLP_WARN << key << ", missing targets"; num_no_tgt_++; feature_reader_.Next(); continue; }
+        const Posterior &target = target_reader_.Value(key);
+        if (rows != (int32)target.size()) {
+          ASLP_WARN << key << ", length miss-match between feats and targers, skip";
+          num_len_mismatch_++;
+          feature_reader_.Next();
+          continue;
+        }
+        if (transform_ != NULL) batcher_.SetUtterance(s, dev_out_, target, read_opts_.skip_width, skip_offset_);
+        else batcher_.SetUtterance(s, raw, target, read_opts_.skip_width, skip_offset_);
+        keys_[s] = key;
+        new_utt_flags_[s] = 1;
+        feature_reader_.Next();
+        break;
+      }
+    }
+  }
+  void GatherBatch(CuMatrix *feat, std::vector<BaseFloat> *frame_mask) {
+    read_done_ = !batcher_.SequenceBatch(read_opts_.batch_size, read_opts_.targets_delay, read_opts_.skip_width, skip_offset_, feat);
+    *frame_mask = batcher_.Plan().mask;
+  }
   void AddNewUtt() {  // data-reader.cc:200-270
     for (int s = 0; s < read_opts_.num_stream; s++) {
       if (curt_[s] < lent_[s]) { new_utt_flags_[s] = 0; continue; }
@@ -563,6 +626,154 @@ class SequenceDataReader {
   Nnet *transform_ = NULL;
   CuMatrix dev_in_, dev_out_;
   HostMatrix transformed_;
+  const bool host_batch_;   // aslp_stream_batch_on_host / ASLP_STREAM_BATCH_HOST=1 when the reader was made: the host assembly above
+  StreamBatcher batcher_;
+  std::vector<int32> labels_host_;
+  HostVector mask_host_;
+};
+
+// ---- ChunkDataReader: the batches of latency-controlled BLSTM training (aslp-nnet-train-blstm-streams-lc.cc:170-250 and its twin in
+// aslp-nnet-train-lc-blstm-streams-worker.cc) ---------------------------------------------------------------------------------------------
+// num-stream utterances advance in parallel; a batch is (chunk-size + right-splice) frames per stream, rows t*S + s, with a frame mask that
+// is 1 on the chunk frames of live streams; padding rows are zero features with the utterance's last target (masked out anyway; a stream
+// that never got an utterance has none); each stream then rewinds by right-splice frames; an exhausted stream takes the next utterance
+// (flag in NewUttFlags) at the next call.  Every utterance goes through `transform` (an empty Nnet copies) on the device.
+// By default it stays there and the batch is gathered from it (StreamBatcher); under aslp_stream_batch_on_host(1) / ASLP_STREAM_BATCH_HOST=1
+// the utterance comes back to the host and the batch is assembled and uploaded as the tools did it before the gather existed.
+class ChunkDataReader {
+ public:
+  ChunkDataReader(const std::string &feature_rspecifier, const std::string &targets_rspecifier, Nnet *transform, int32 num_stream,
+                  int32 chunk_size, int32 right_splice, int32 drop_len, int32 feat_dim)
+      : feature_reader_(feature_rspecifier), target_reader_(targets_rspecifier), transform_(transform), num_stream_(num_stream),
+        chunk_size_(chunk_size), right_splice_(right_splice), drop_len_(drop_len), feat_dim_(feat_dim),
+        host_batch_(aslp_stream_batch_on_host_get() != 0), batcher_(num_stream), keys_(num_stream), new_utt_flags_(num_stream, 0) {
+    ASLP_ASSERT(transform != NULL);
+    if (host_batch_) {
+      feats_.resize(num_stream);
+      targets_.resize(num_stream);
+      curt_.assign(num_stream, 0);
+      lent_.assign(num_stream, 0);
+      frame_mask_.assign((size_t)(chunk_size + right_splice) * num_stream, 0.0f);
+      feat_.Resize((chunk_size + right_splice) * num_stream, feat_dim);
+      target_.resize((size_t)(chunk_size + right_splice) * num_stream);
+    }
+  }
+  // false: every stream is exhausted and the table is read through; *cu_feat is as it was
+  bool Next(CuMatrix *cu_feat) {
+    AddNewUtt();
+    if (!host_batch_) {
+      if (!batcher_.ChunkBatch(chunk_size_, right_splice_, feat_dim_, cu_feat)) return false;
+      have_target_ = false;
+      return true;
+    }
+    const int32 num_stream = num_stream_, batch_size = chunk_size_ + right_splice_, chunk_size = chunk_size_, feat_dim = feat_dim_;
+    std::vector<int32> &curt = curt_, &lent = lent_;
+    int done = 1;
+    for (int s = 0; s < num_stream; s++)
+      if (curt[s] < lent[s]) done = 0;
+    if (done) return false;
+    for (int t = 0; t < batch_size; t++) {
+      for (int s = 0; s < num_stream; s++) {
+        const size_t row = (size_t)t * num_stream + s;
+        if (curt[s] < lent[s]) {
+          frame_mask_[row] = t >= chunk_size ? 0.0f : 1.0f;
+          target_[row] = targets_[s][curt[s]];
+          std::copy(feats_[s].data.begin() + (size_t)curt[s] * feat_dim, feats_[s].data.begin() + (size_t)(curt[s] + 1) * feat_dim,
+                    feat_.data.begin() + row * feat_dim);
+        } else {
+          frame_mask_[row] = 0.0f;
+          if (lent[s] > 0) target_[row] = targets_[s][lent[s] - 1];
+          else target_[row].clear();
+          std::fill(feat_.data.begin() + row * feat_dim, feat_.data.begin() + (row + 1) * feat_dim, 0.0f);
+        }
+        curt[s]++;
+      }
+    }
+    for (int s = 0; s < num_stream; s++) curt[s] = curt[s] - right_splice_;
+    *cu_feat = feat_;
+    return true;
+  }
+  const std::vector<BaseFloat> &FrameMask() const { return host_batch_ ? frame_mask_ : batcher_.Plan().mask; }
+  const std::vector<int32> &NewUttFlags() const { return new_utt_flags_; }
+  int32 NumNoTargets() const { return num_no_tgt_; }
+  int32 NumOtherError() const { return num_other_error_; }
+  // Xent of the batch handed out last.  One-hot targets go to the loss as device labels (Xent::EvalLabels, where Xent::Eval takes a
+  // Posterior of one-hot targets as well: same diff, same sums); anything else, and everything on the host path, as a Posterior.
+  void EvalXent(Xent *xent, const CuMatrixBase &nnet_out, CuMatrix *obj_diff) {
+    if (host_batch_) { xent->Eval(frame_mask_, nnet_out, target_, obj_diff); return; }
+    if (batcher_.BatchLabels(nnet_out.NumCols(), &labels_host_)) {
+      labels_dev_ = labels_host_;
+      mask_host_.data = batcher_.Plan().mask;
+      mask_dev_ = mask_host_;
+      xent->EvalLabels(mask_dev_, nnet_out, labels_dev_, obj_diff);
+      return;
+    }
+    if (!have_target_) { batcher_.BatchTargets(&target_); have_target_ = true; }
+    xent->Eval(batcher_.Plan().mask, nnet_out, target_, obj_diff);
+  }
+
+ private:
+  void AddNewUtt() {  // feed exhausted streams with a new utterance
+    for (int s = 0; s < num_stream_; s++) {
+      if (host_batch_ ? curt_[s] < lent_[s] : !batcher_.StreamDone(s)) { new_utt_flags_[s] = 0; continue; }
+      while (!feature_reader_.Done()) {
+        const std::string key = feature_reader_.Key();
+        const HostMatrix &mat = feature_reader_.Value();
+        if (drop_len_ > 0 && mat.rows > drop_len_) { ASLP_WARN << key << ", too long, droped"; feature_reader_.Next(); continue; }
+        const bool on_host_still = !host_batch_ && transform_->NumComponents() == 0;   // nothing to apply: straight into the stream's buffer
+        if (!on_host_still) {
+          cu_in_ = mat;
+          transform_->Feedforward(cu_in_, &feat_transf_);
+        }
+        const int32 rows = on_host_still ? mat.rows : feat_transf_.NumRows();
+        if (!target_reader_.HasKey(key)) { ASLP_WARN << key << ", missing targets"; num_no_tgt_++; feature_reader_.Next(); continue; }
+        const Posterior &tgt = target_reader_.Value(key);
+        if (rows != (int32)tgt.size()) {
+          ASLP_WARN << key << ", length miss-match between feats and targets, skip";
+          num_other_error_++;
+          feature_reader_.Next();
+          continue;
+        }
+        keys_[s] = key;
+        if (host_batch_) {
+          feat_transf_.CopyToMat(&feats_[s]);
+          targets_[s] = tgt;
+          curt_[s] = 0;
+          lent_[s] = feats_[s].rows;
+        } else if (on_host_still) {
+          batcher_.SetUtterance(s, mat, tgt);
+        } else {
+          batcher_.SetUtterance(s, feat_transf_, tgt);
+        }
+        new_utt_flags_[s] = 1;
+        feature_reader_.Next();
+        break;
+      }
+    }
+  }
+  SequentialBaseFloatMatrixReader feature_reader_;
+  RandomAccessPosteriorReader target_reader_;
+  Nnet *transform_;
+  const int32 num_stream_, chunk_size_, right_splice_, drop_len_, feat_dim_;
+  const bool host_batch_;
+  StreamBatcher batcher_;
+  std::vector<std::string> keys_;
+  std::vector<int32> new_utt_flags_;
+  int32 num_no_tgt_ = 0, num_other_error_ = 0;
+  CuMatrix cu_in_, feat_transf_;
+  // the host assembly
+  std::vector<HostMatrix> feats_;
+  std::vector<Posterior> targets_;
+  std::vector<int32> curt_, lent_;
+  std::vector<BaseFloat> frame_mask_;
+  HostMatrix feat_;
+  // the batch's targets: the host assembly's, or the device path's where the labels do not serve
+  Posterior target_;
+  bool have_target_ = false;
+  std::vector<int32> labels_host_;
+  HostVector mask_host_;
+  CuArray<int32> labels_dev_;
+  CuVector mask_dev_;
 };
 
 }  // namespace aslp

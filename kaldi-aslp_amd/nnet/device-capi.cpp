@@ -46,5 +46,6 @@ int aslp_device_get_free_memory(char *buf, int buflen, long long *free_bytes, lo
   if (total_bytes) *total_bytes = t;
   DEV_END
 }
+long long aslp_device_to_host_syncs(void) { return DeviceToHostSyncs(); }
 
 }  // extern "C"

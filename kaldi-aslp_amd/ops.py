@@ -396,6 +396,49 @@ def ctc_token_errors(acts, labels, input_lengths=None):
     return errors, [hyps[n, :hyp_lens[n]].tolist() for n in range(mb)]
 
 
+def gather_stream_rows(dst, sources, src_frame):
+    """aslp_gather_stream_rows (include/aslp_kernels.h): dst [B*S x D] (a device tensor or a view with a row stride >= D); row r receives row
+    src_frame[r] of sources[r % S], or +0.0 where src_frame[r] == -1.  sources: S device matrices with at least D columns (views welcome), None
+    for a stream without rows.  src_frame: B*S host integers.  A plan that points outside a source raises and launches nothing."""
+    import numpy as np
+    from ._lib import StreamSrc
+    _chk(dst)
+    S = len(sources)
+    rows, D = dst.shape
+    if S == 0 or rows % S:
+        raise ValueError("dst rows must be a multiple of the number of streams")
+    plan = np.ascontiguousarray(src_frame, dtype=np.int32)
+    if plan.shape != (rows,):
+        raise ValueError("src_frame must hold one entry per dst row")
+    table = (StreamSrc * S)()
+    for s, m in enumerate(sources):
+        if m is None or m.shape[0] == 0:
+            table[s].base, table[s].stride, table[s].rows = None, 0, 0
+            continue
+        _chk(m)
+        if m.dim() != 2 or m.shape[1] < D:
+            raise ValueError("source %d must be a matrix of at least %d columns" % (s, D))
+        table[s].base, table[s].stride, table[s].rows = m.data_ptr(), dim(m).stride, m.shape[0]
+    table_dev = torch.frombuffer(bytearray(bytes(table)), dtype=torch.uint8).to(dst.device)
+    plan_dev = torch.from_numpy(plan).to(dst.device)
+    rc = lib.aslp_gather_stream_rows(ptr(dst), dim(dst).stride, rows // S, S, D, table, ptr(table_dev), plan.ctypes.data_as(C.POINTER(C.c_int32)),
+                                     ptr(plan_dev))
+    check_error()
+    if rc != 0:
+        raise RuntimeError("aslp_gather_stream_rows refused its arguments")
+
+
+def stream_batch_on_host(n):
+    """1: SequenceDataReader and the chunked stream tools assemble their batches on the host; 0: gathered on the device; -1: what
+    ASLP_STREAM_BATCH_HOST said.  Read when a reader is opened."""
+    lib.aslp_stream_batch_on_host(int(n))
+
+
+def device_to_host_syncs():
+    """aslp_device_to_host_syncs (include/aslp_device.h): device-to-host copies of the engine so far, each of which waited for the stream"""
+    return int(lib.aslp_device_to_host_syncs())
+
+
 def ctc_errors_on_host(n):
     """1: the token errors of the CTC losses (and of ctc_token_errors) take the host loop; 0: the device kernel wherever it serves the batch;
     -1: what ASLP_CTC_ERRORS_HOST said"""

@@ -72,14 +72,20 @@ int Main_aslp_nnet_train_lstm_streams(int argc, char *argv[]) {
     CuMatrix nnet_out, obj_diff, nnet_in;
     std::vector<BaseFloat> frame_mask;
     Posterior nnet_tgt;
+    Xent *xent = dynamic_cast<Xent *>(loss);   // Xent takes one-hot targets as device labels (no Posterior is copied row by row); Mse the Posterior
+    CuArray<int32> labels_dev;
+    CuVector mask_dev;
     while (!reader.Done()) {
-      reader.ReadData(&nnet_in, &nnet_tgt, &frame_mask);
+      bool labels_on_device = false;
+      if (xent != NULL) labels_on_device = reader.ReadData(&nnet_in, &nnet_tgt, &frame_mask, nnet.OutputDim(), &labels_dev, &mask_dev);
+      else reader.ReadData(&nnet_in, &nnet_tgt, &frame_mask);
       if (nnet_in.NumRows() == 0) break;  // no usable utterance at all
       std::vector<int32> new_utt_flags = reader.GetNewUttFlags();
       nnet.ResetLstmStreams(new_utt_flags);
       if (!crossvalidate) nnet.Propagate(nnet_in, &nnet_out);
       else nnet.Feedforward(nnet_in, &nnet_out);
-      loss->Eval(frame_mask, nnet_out, nnet_tgt, &obj_diff);
+      if (labels_on_device) xent->EvalLabels(mask_dev, nnet_out, labels_dev, &obj_diff);
+      else loss->Eval(frame_mask, nnet_out, nnet_tgt, &obj_diff);
       if (!crossvalidate) nnet.Backpropagate(obj_diff, NULL);
       if (g_verbose_level >= 1 && total_frames == 0) {
         ASLP_VLOG(1) << "### After " << total_frames << " frames,";
@@ -186,19 +192,23 @@ int Main_aslp_nnet_train_lstm_streams_skip(int argc, char *argv[]) {
     CuMatrix nnet_in, nnet_out, obj_diff;
     std::vector<BaseFloat> frame_mask;
     Posterior nnet_tgt;
+    CuArray<int32> labels_dev;
+    CuVector mask_dev;
     const int32 passes = read_opts.skip_width > 1 ? read_opts.skip_width : 1;
     for (int32 skip_offset = 0; skip_offset < passes; skip_offset++) {  // every pass reopens both tables (:163-164)
       SequenceDataReader reader(feature_rspecifier, targets_rspecifier, read_opts);
       reader.SetSkipOffset(skip_offset);
       if (nnet_transf.NumComponents() > 0) reader.SetFeatureTransform(&nnet_transf);
       while (!reader.Done()) {
-        reader.ReadData(&nnet_in, &nnet_tgt, &frame_mask);
+        // one-hot targets come as device labels (no Posterior is copied row by row), anything else as the Posterior
+        const bool labels_on_device = reader.ReadData(&nnet_in, &nnet_tgt, &frame_mask, nnet.OutputDim(), &labels_dev, &mask_dev);
         if (reader.Done()) break;  // all streams exhausted: the reference leaves the loop before touching the net (:238)
         std::vector<int32> new_utt_flags = reader.GetNewUttFlags();
         nnet.ResetLstmStreams(new_utt_flags);
         if (!crossvalidate) nnet.Propagate(nnet_in, &nnet_out);
         else nnet.Feedforward(nnet_in, &nnet_out);
-        xent.Eval(frame_mask, nnet_out, nnet_tgt, &obj_diff);
+        if (labels_on_device) xent.EvalLabels(mask_dev, nnet_out, labels_dev, &obj_diff);
+        else xent.Eval(frame_mask, nnet_out, nnet_tgt, &obj_diff);
         if (!crossvalidate) nnet.Backpropagate(obj_diff, NULL);
         int32 frame_progress = 0, num_done_progress = 0;
         for (BaseFloat m : frame_mask) frame_progress += (int32)m;
@@ -591,7 +601,6 @@ int Main_aslp_nnet_train_blstm_streams_lc(int argc, char *argv[]) {
     int32 drop_len = 0;
     po.Register("drop-len", &drop_len, "if Sentence frame length greater than drop_len,then drop it, default(0, no drop)");
     po.Read(argc, argv);
-    const int32 batch_size = chunk_size + right_splice;
     if (po.NumArgs() != 4 - (crossvalidate ? 1 : 0)) { po.PrintUsage(); exit(1); }
     std::string feature_rspecifier = po.GetArg(1), targets_rspecifier = po.GetArg(2), model_filename = po.GetArg(3);
     std::string target_model_filename;
@@ -606,80 +615,24 @@ int Main_aslp_nnet_train_blstm_streams_lc(int argc, char *argv[]) {
     nnet.SetChunkSize(chunk_size);
 
     int64_t total_frames = 0;
-    SequentialBaseFloatMatrixReader feature_reader(feature_rspecifier);
-    RandomAccessPosteriorReader target_reader(targets_rspecifier);
     Xent xent;
     Mse mse;
     Timer time;
     RandomizerMask randomizer_mask(rnd_opts);   // unused by this tool, as in the reference (aslp-nnet-train-blstm-streams-lc.cc:151), but its construction seeds the generator and says so in the log
     ASLP_LOG << (crossvalidate ? "CROSS-VALIDATION" : "TRAINING") << " STARTED";
     int32 num_done = 0, num_no_tgt_mat = 0, num_other_error = 0, num_sentence = 0;
-    std::vector<std::string> keys(num_stream);
-    std::vector<HostMatrix> feats(num_stream);
-    std::vector<Posterior> targets(num_stream);
-    std::vector<int32> curt(num_stream, 0), lent(num_stream, 0), new_utt_flags(num_stream, 0);
     const int32 feat_dim = nnet.InputDim();
-    std::vector<BaseFloat> frame_mask((size_t)batch_size * num_stream, 0.0f);
-    HostMatrix feat(batch_size * num_stream, feat_dim);
-    Posterior target((size_t)batch_size * num_stream);
-    CuMatrix cu_in, feat_transf, cu_feat, nnet_out, obj_diff;
+    // the utterances, the chunk batches and their targets: ChunkDataReader (data-reader.h), shared with the LC worker
+    ChunkDataReader reader(feature_rspecifier, targets_rspecifier, &nnet_transf, num_stream, chunk_size, right_splice, drop_len, feat_dim);
+    CuMatrix cu_feat, nnet_out, obj_diff;
 
-    while (1) {
-      for (int s = 0; s < num_stream; s++) {  // feed exhausted streams with a new utterance
-        if (curt[s] < lent[s]) { new_utt_flags[s] = 0; continue; }
-        while (!feature_reader.Done()) {
-          const std::string key = feature_reader.Key();
-          const HostMatrix &mat = feature_reader.Value();
-          if (drop_len > 0 && mat.rows > drop_len) { ASLP_WARN << key << ", too long, droped"; feature_reader.Next(); continue; }
-          cu_in = mat;
-          nnet_transf.Feedforward(cu_in, &feat_transf);
-          if (!target_reader.HasKey(key)) { ASLP_WARN << key << ", missing targets"; num_no_tgt_mat++; feature_reader.Next(); continue; }
-          const Posterior &tgt = target_reader.Value(key);
-          if (feat_transf.NumRows() != (int32)tgt.size()) {
-            ASLP_WARN << key << ", length miss-match between feats and targets, skip";
-            num_other_error++;
-            feature_reader.Next();
-            continue;
-          }
-          keys[s] = key;
-          feat_transf.CopyToMat(&feats[s]);
-          targets[s] = tgt;
-          curt[s] = 0;
-          lent[s] = feats[s].rows;
-          new_utt_flags[s] = 1;
-          feature_reader.Next();
-          break;
-        }
-      }
-      int done = 1;
-      for (int s = 0; s < num_stream; s++)
-        if (curt[s] < lent[s]) done = 0;
-      if (done) break;
-      // fill a multi-stream batch: mask 1 = chunk frame of a live stream; padding rows are zero features with the
-      // utterance's last target (masked out anyway); a stream that never got an utterance has no last target
-      for (int t = 0; t < batch_size; t++) {
-        for (int s = 0; s < num_stream; s++) {
-          const size_t row = (size_t)t * num_stream + s;
-          if (curt[s] < lent[s]) {
-            frame_mask[row] = t >= chunk_size ? 0.0f : 1.0f;
-            target[row] = targets[s][curt[s]];
-            std::copy(feats[s].data.begin() + (size_t)curt[s] * feat_dim, feats[s].data.begin() + (size_t)(curt[s] + 1) * feat_dim,
-                      feat.data.begin() + row * feat_dim);
-          } else {
-            frame_mask[row] = 0.0f;
-            if (lent[s] > 0) target[row] = targets[s][lent[s] - 1];
-            else target[row].clear();
-            std::fill(feat.data.begin() + row * feat_dim, feat.data.begin() + (row + 1) * feat_dim, 0.0f);
-          }
-          curt[s]++;
-        }
-      }
-      for (int s = 0; s < num_stream; s++) curt[s] = curt[s] - right_splice;
+    while (reader.Next(&cu_feat)) {
+      const std::vector<int32> &new_utt_flags = reader.NewUttFlags();
+      const std::vector<BaseFloat> &frame_mask = reader.FrameMask();
       nnet.ResetLstmStreams(new_utt_flags);
-      cu_feat = feat;
       if (!crossvalidate) nnet.Propagate(cu_feat, &nnet_out);
       else nnet.Feedforward(cu_feat, &nnet_out);
-      if (objective_function == "xent") xent.Eval(frame_mask, nnet_out, target, &obj_diff);
+      if (objective_function == "xent") reader.EvalXent(&xent, nnet_out, &obj_diff);
       else ASLP_ERR << "Unknown objective function code : " << objective_function;
       if (!crossvalidate) nnet.Backpropagate(obj_diff, NULL);
       if (g_verbose_level >= 1 && total_frames == 0) {
@@ -704,6 +657,8 @@ int Main_aslp_nnet_train_blstm_streams_lc(int argc, char *argv[]) {
       if (dump_interval > 0 && (num_done - num_done_progress) / dump_interval != (num_done / dump_interval) && !crossvalidate)
         nnet.Write(target_model_filename + "_utt" + std::to_string(num_done), binary);
     }
+    num_no_tgt_mat = reader.NumNoTargets();
+    num_other_error = reader.NumOtherError();
     if (g_verbose_level >= 1) {
       ASLP_VLOG(1) << "### After " << total_frames << " frames,";
       ASLP_VLOG(1) << nnet.InfoPropagate();
