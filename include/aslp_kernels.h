@@ -430,6 +430,26 @@ void aslp_coop_convert(int on);
 int aslp_xent_eval_rows(const float *net_out, MatrixDim d, const int32_cuda *labels, const float *frame_weights, float *diff, int diff_stride,
                         double *rowstats_out, int softmax, const aslp_planes_out *diff_planes);
 void aslp_xent_sum_rowstats(const double *rowstats, int rows, int batches, double *stats_dev);
+/* Mse::Eval (nnet-loss.cc:205-258) in one pass over net_out and tgt [d.rows x d.cols].  Per element in fp32, every operation rounded on
+ * its own:  e = (y - t) * w[row];  diff = e, or e * scale as a second rounding when scale != 1 (MultiTaskLoss' Scale);  q = (e * e) * w[row]
+ * -- the bits of AddMat(-1), MulRowsVec, MulElements, MulRowsVec.  row_loss[row] (double) = the sum of the row's q in a fixed order, no
+ * atomics: two calls give the same bits.  The factor 0.5 and the minibatch total are the caller's.
+ * diff_out (nullable): with diff_out->parts, one maximum of the finite |diff| per workgroup is left there (nparts of them, at most 256),
+ * from which a conversion of diff takes its scale (aslp_planes_convert_with_parts / the engine's PlaneSet).  Planes are never written: no
+ * bound of |y - t| is known before the launch.
+ * 16-byte accesses when net_out, tgt and diff are 16-byte aligned and all three strides are multiples of 4; one column per access
+ * otherwise (a column window at an odd offset of a wider matrix).  Neither form reads a float at a column >= d.cols or writes outside
+ * [rows x cols] of diff.  Returns 1, or 0 = refused (a null pointer other than diff_out, a size <= 0, a stride below d.cols): the error
+ * string is set and nothing is launched. */
+int aslp_mse_eval(const float *net_out, MatrixDim d, const float *tgt, int tgt_stride, const float *frame_weights, float scale, float *diff,
+                  int diff_stride, double *row_loss /* [d.rows] */, aslp_planes_out *diff_out /* nullable */);
+/* ... which also leaves, in *frames_out (nullable), the frame count of a minibatch whose weights only the device holds: the weights summed in
+ * index order in double and truncated toward zero (Mse::EvalDevice). */
+int aslp_mse_eval_w(const float *net_out, MatrixDim d, const float *tgt, int tgt_stride, const float *frame_weights, float scale, float *diff,
+                    int diff_stride, double *row_loss, aslp_planes_out *diff_out, double *frames_out);
+/* `batches` blocks of rows + 1 doubles each, consecutive in memory (a batch's row_loss and, behind it, its frames_out):
+ * sums[2 b] = the sum of block b's rows in a fixed order, sums[2 b + 1] = the double behind them. */
+void aslp_mse_batch_sums(const double *pending, int rows, int batches, double *sums /* [2 x batches] */);
 /* cudaF_diff_sigmoid which also leaves the planes of its result: |e y (1 - y)| <= max |e| / 4 with max |e| from the n_parts per-workgroup
  * maxima the producer of e left (aslp_gemm_epilogue.cmax_parts).  The kernel stores the bound to out_planes->slot itself.  Returns 1 if the
  * planes were written, 0 if only eout was (operands not 16-byte aligned, no maxima). */

@@ -18,6 +18,7 @@ extern "C" {
 
 typedef struct aslp_nnet_s *aslp_nnet_t;
 typedef struct aslp_xent_s *aslp_xent_t;
+typedef struct aslp_mse_s *aslp_mse_t;
 
 const char *aslp_nnet_last_error(void);
 void aslp_set_verbose(int level);
@@ -92,6 +93,21 @@ int aslp_xent_get_stats(aslp_xent_t x, double stats[5]);      /* frames, correct
  * (nnet-nnet.cc:70-154 + nnet-loss.cc:63; the loop body of aslp-nnet-train-frame.cc:109-131). */
 int aslp_nnet_train_step_xent(aslp_nnet_t n, aslp_xent_t x, const float *in, int rows, int cols, int stride,
                               const int32_t *labels, const float *frame_weights);
+
+/* ---- Mse (nnet-loss.h:120-164) -------------------------------------------------------------- */
+int aslp_mse_create(aslp_mse_t *out);
+void aslp_mse_free(aslp_mse_t m);
+/* net_out, targets [rows x cols], frame_weights [rows] (NULL = ones), diff [rows x cols]: all device.  One launch, nothing read back:
+ * the loss and the frame count (int32 of the weights' sum, per minibatch) reach the host with aslp_mse_report / aslp_mse_get_stats, and
+ * so does the error of a loss that is not finite. */
+int aslp_mse_eval_batch(aslp_mse_t m, const float *net_out, int rows, int cols, int stride, const float *targets, int tgt_stride,
+                        const float *frame_weights, float *diff, int diff_stride);
+int aslp_mse_report(aslp_mse_t m, char *buf, int buflen);   /* Mse::Report nnet-loss.cc:277 */
+int aslp_mse_get_stats(aslp_mse_t m, double stats[3]);      /* frames, loss, num_tgt */
+/* One whole training step with nothing on the host: Propagate -> Mse::Eval -> Backpropagate (the loop body of aslp-nnet-train-mse.cc).
+ * Mse reads the network's output: a final Softmax is never folded away. */
+int aslp_nnet_train_step_mse(aslp_nnet_t n, aslp_mse_t m, const float *in, int rows, int cols, int stride, const float *targets,
+                             int tgt_stride, const float *frame_weights);
 
 /* ---- WarpCtc (aslp-nnet/warp-ctc.h:29-113) -------------------------------------------------- */
 typedef struct aslp_warpctc_s *aslp_warpctc_t;

@@ -264,6 +264,9 @@ _sig("aslp_softmax_xent_supported", _i, _i)
 _sig("aslp_xent_eval_p", _i, _vp, _md, _vp, _vp, _vp, _i, _vp, _i, C.POINTER(PlanesOut))
 _sig("aslp_xent_eval_rows", _i, _vp, _md, _vp, _vp, _vp, _i, _vp, _i, C.POINTER(PlanesOut))
 _sig("aslp_xent_sum_rowstats", None, _vp, _i, _i, _vp)
+_sig("aslp_mse_eval", _i, _vp, _md, _vp, _i, _vp, C.c_float, _vp, _i, _vp, C.POINTER(PlanesOut))
+_sig("aslp_mse_eval_w", _i, _vp, _md, _vp, _i, _vp, C.c_float, _vp, _i, _vp, C.POINTER(PlanesOut), _vp)
+_sig("aslp_mse_batch_sums", None, _vp, _i, _i, _vp)
 _sig("aslp_device_shared", None, _i)
 _sig("aslp_coop_convert", None, _i)
 _sig("aslp_softmax_xent_eval", None, _vp, _md, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _i)

@@ -1245,6 +1245,101 @@ __global__ void xent_apply_kernel(const double *sums, int batches, double *stats
   for (int k = 0; k < 5; k++) stats[k] = a[k];
 }
 
+// ---- Mse ------------------------------------------------------------------------------
+// Mse::Eval in one pass over net_out and the targets (aslp_mse_eval).  One wave per row, four rows per workgroup at a time, at most 256
+// workgroups (the maxima array of aslp_planes_out holds that many); a lane takes the row's columns (VEC: its groups of four columns) lane,
+// lane + 64, ...  Per element, every operation rounded on its own: e = (y - t) w, diff = e (or e * scale), q = (e e) w -- the bits of
+// AddMat(-1), MulRowsVec, [Scale], MulElements, MulRowsVec.  row_loss[r] = sum of the row's q in double: a lane's columns in rising
+// order, then the wave's butterfly -- the same order in every call, no atomics.  parts (nullable): the workgroup's largest finite |diff|.
+// VEC: 16-byte accesses; the group that holds a row's last column is read and written column by column (s16_load4_ragged), so neither
+// form touches a float at a column >= cols (row padding, or the neighbouring task's columns of a MultiTask window).
+// frames_out (nullable): one more workgroup, the launch's last, leaves trunc(sum of the weights, in index order, in double) there.
+template <bool VEC>
+__global__ void __launch_bounds__(kPanelThreads) mse_rows_kernel(const float *y, int ldy, const float *t, int ldt, const float *__restrict__ fw,
+                                                                 float scale, float *diff, int ldd, int rows, int cols,
+                                                                 double *__restrict__ row_loss, float *__restrict__ parts,
+                                                                 double *__restrict__ frames_out) {
+#pragma clang fp contract(off)
+  __shared__ float red[kPanelWaves];
+  const int nwg = frames_out != nullptr ? (int)gridDim.x - 1 : (int)gridDim.x;
+  if ((int)blockIdx.x == nwg) {   // (uniform: the whole workgroup)
+    if (threadIdx.x == 0) {
+      double s = 0.0;
+      for (int r = 0; r < rows; r++) s += (double)fw[r];
+      frames_out[0] = trunc(s);
+    }
+    return;
+  }
+  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+  const bool scaled = scale != 1.0f;
+  float m = 0.f;
+  for (int r = (int)blockIdx.x * kPanelWaves + wave; r < rows; r += nwg * kPanelWaves) {
+    const float w = fw[r];
+    const float *yr = y + (long)r * ldy, *tr = t + (long)r * ldt;
+    float *dr = diff + (long)r * ldd;
+    double acc = 0.0;
+    if constexpr (VEC) {
+      const int c4 = (cols + 3) >> 2;
+      for (int g = lane; g < c4; g += kWave) {
+        const int c = 4 * g;
+        const float4 yv = s16_load4_ragged(yr, c, cols), tv = s16_load4_ragged(tr, c, cols);
+        const float ya[4] = {yv.x, yv.y, yv.z, yv.w}, ta[4] = {tv.x, tv.y, tv.z, tv.w};
+        float d[4];
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+          const float e = (ya[i] - ta[i]) * w;
+          d[i] = scaled ? e * scale : e;
+          const float q = (e * e) * w;
+          if (c + i < cols) acc += (double)q;
+        }
+        if (c + 4 <= cols) {
+          const float4 dv = make_float4(d[0], d[1], d[2], d[3]);
+          m = s16_absmax4(m, dv);
+          *reinterpret_cast<float4 *>(dr + c) = dv;
+        } else {   // (the row ends inside this group: nothing is written behind its last column, nothing behind it counts)
+          for (int i = 0; i < 4 && c + i < cols; i++) {
+            const float a = fabsf(d[i]);
+            m = fmaxf(m, a < 3.0e38f ? a : 0.f);
+            dr[c + i] = d[i];
+          }
+        }
+      }
+    } else {
+      for (int c = lane; c < cols; c += kWave) {
+        const float e = (yr[c] - tr[c]) * w;
+        const float dv = scaled ? e * scale : e;
+        const float q = (e * e) * w;
+        acc += (double)q;
+        const float a = fabsf(dv);
+        m = fmaxf(m, a < 3.0e38f ? a : 0.f);
+        dr[c] = dv;
+      }
+    }
+    acc = wave_sum_d(acc);
+    if (lane == 0) row_loss[r] = acc;
+  }
+  if (parts != nullptr) {   // (uniform)
+    m = wg_max(m, red);
+    if (threadIdx.x == 0) parts[blockIdx.x] = m;
+  }
+}
+// What Mse parks batch after batch (aslp_mse_eval's row_loss, `rows` doubles, and one double behind them: the batch's frame count where the
+// device formed it) summed per batch: sums[2 b] = the batch's loss sum (thread t: rows t, t + 256, ... in rising order; the wave's
+// butterfly; the four waves in order), sums[2 b + 1] = the double behind its rows.  One workgroup per batch.
+__global__ void __launch_bounds__(256) mse_batch_sums_kernel(const double *pending, int rows, double *sums) {
+  __shared__ double sh[4];
+  const double *p = pending + (size_t)blockIdx.x * ((size_t)rows + 1);
+  double a = 0.0;
+  for (int r = threadIdx.x; r < rows; r += 256) a += p[r];
+  a = wave_sum_d(a);
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = a;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    sums[2 * (size_t)blockIdx.x] = ((sh[0] + sh[1]) + sh[2]) + sh[3];
+    sums[2 * (size_t)blockIdx.x + 1] = p[rows];
+  }
+}
+
 }  // namespace
 
 static bool g_coop_convert_on = true;   // aslp_coop_convert (tests: the two-launch conversion as the reference)
@@ -1581,6 +1676,38 @@ void aslp_softmax_xent_eval(const float *acts, MatrixDim d, const float *tgt, in
                             const float *frame_weights, float *diff, int diff_stride, double *stats_dev, float *post_out, int post_stride) {
   if (!aslp_softmax_xent_supported(d.cols)) { set_error("aslp_softmax_xent_eval: unsupported number of classes"); return; }
   xent_eval_impl(acts, d, tgt, tgt_stride, labels, frame_weights, diff, diff_stride, stats_dev, true, post_out, post_stride);
+}
+
+// Mse::Eval in one launch (mse_rows_kernel above).  16-byte accesses where all three matrices allow them, one column per access elsewhere
+// (a MultiTask window at an odd column of a wider matrix).  0 = refused, nothing launched.
+int aslp_mse_eval_w(const float *net_out, MatrixDim d, const float *tgt, int tgt_stride, const float *frame_weights, float scale, float *diff,
+                    int diff_stride, double *row_loss, aslp_planes_out *diff_out, double *frames_out) {
+  if (diff_out) { diff_out->nparts = 0; diff_out->planes_written = 0; }
+  if (!net_out || !tgt || !frame_weights || !diff || !row_loss) { set_error("aslp_mse_eval: null argument"); return 0; }
+  if (d.rows <= 0 || d.cols <= 0 || d.stride < d.cols || tgt_stride < d.cols || diff_stride < d.cols) {
+    set_error("aslp_mse_eval: sizes must be positive and no stride smaller than the number of columns");
+    return 0;
+  }
+  const bool vec = aligned16(net_out) && aligned16(tgt) && aligned16(diff) && (d.stride & 3) == 0 && (tgt_stride & 3) == 0 && (diff_stride & 3) == 0;
+  float *parts = diff_out ? diff_out->parts : nullptr;
+  const int g = std::min((d.rows + kPanelWaves - 1) / kPanelWaves, kS16ConvParts);
+  const dim3 grid(g + (frames_out ? 1 : 0));
+  if (vec) hipLaunchKernelGGL((mse_rows_kernel<true>), grid, dim3(kPanelThreads), 0, cur_stream(), net_out, d.stride, tgt, tgt_stride, frame_weights, scale,
+                              diff, diff_stride, d.rows, d.cols, row_loss, parts, frames_out);
+  else hipLaunchKernelGGL((mse_rows_kernel<false>), grid, dim3(kPanelThreads), 0, cur_stream(), net_out, d.stride, tgt, tgt_stride, frame_weights, scale,
+                          diff, diff_stride, d.rows, d.cols, row_loss, parts, frames_out);
+  check_launch("mse_eval");
+  if (parts) diff_out->nparts = g;
+  return 1;
+}
+int aslp_mse_eval(const float *net_out, MatrixDim d, const float *tgt, int tgt_stride, const float *frame_weights, float scale, float *diff,
+                  int diff_stride, double *row_loss, aslp_planes_out *diff_out) {
+  return aslp_mse_eval_w(net_out, d, tgt, tgt_stride, frame_weights, scale, diff, diff_stride, row_loss, diff_out, nullptr);
+}
+void aslp_mse_batch_sums(const double *pending, int rows, int batches, double *sums) {
+  if (!pending || !sums || rows <= 0 || batches <= 0) return;
+  hipLaunchKernelGGL(mse_batch_sums_kernel, dim3(batches), dim3(256), 0, cur_stream(), pending, rows, sums);
+  check_launch("mse_batch_sums");
 }
 
 }  // extern "C"

@@ -52,6 +52,12 @@ _sig("aslp_xent_eval_batch", _i, _H, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _i
 _sig("aslp_xent_report", _i, _H, C.c_char_p, _i)
 _sig("aslp_xent_get_stats", _i, _H, C.POINTER(C.c_double))
 _sig("aslp_nnet_train_step_xent", _i, _H, _H, _vp, _i, _i, _i, _vp, _vp)
+_sig("aslp_mse_create", _i, C.POINTER(_H))
+_sig("aslp_mse_free", None, _H)
+_sig("aslp_mse_eval_batch", _i, _H, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _i)
+_sig("aslp_mse_report", _i, _H, C.c_char_p, _i)
+_sig("aslp_mse_get_stats", _i, _H, C.POINTER(C.c_double))
+_sig("aslp_nnet_train_step_mse", _i, _H, _H, _vp, _i, _i, _i, _vp, _i, _vp)
 _i32p = C.POINTER(C.c_int32)
 _sig("aslp_warpctc_create", _i, C.POINTER(_H))
 _sig("aslp_warpctc_free", None, _H)
@@ -93,6 +99,39 @@ class Xent:
         st = (C.c_double * 5)()
         _ok(lib.aslp_xent_get_stats(self.h, st))
         return dict(zip(("frames", "correct", "loss", "entropy", "likelyhood"), list(st)))
+
+
+class Mse:
+    """Mse (nnet-loss.h:120-164): one launch per Eval, nothing read back until Report() / GetStats()"""
+
+    def __init__(self):
+        self.h = _H()
+        _ok(lib.aslp_mse_create(C.byref(self.h)))
+
+    def __del__(self):
+        if getattr(self, "h", None) and lib is not None:
+            lib.aslp_mse_free(self.h)
+            self.h = None
+
+    def Eval(self, frame_weights, net_out, targets, diff):
+        """frame_weights: a device vector [rows], or None = ones"""
+        _chk(net_out), _chk(targets), _chk(diff)
+        if frame_weights is not None:
+            _chk(frame_weights)
+        if targets.shape != net_out.shape or diff.shape != net_out.shape:
+            raise ValueError("net_out, targets and diff must have one shape")
+        _ok(lib.aslp_mse_eval_batch(self.h, ptr(net_out), net_out.shape[0], net_out.shape[1], dim(net_out).stride, ptr(targets),
+                                    dim(targets).stride, ptr(frame_weights), ptr(diff), dim(diff).stride))
+
+    def Report(self):
+        buf = C.create_string_buffer(4096)
+        _ok(lib.aslp_mse_report(self.h, buf, 4096))
+        return buf.value.decode()
+
+    def GetStats(self):
+        st = (C.c_double * 3)()
+        _ok(lib.aslp_mse_get_stats(self.h, st))
+        return dict(zip(("frames", "loss", "num_tgt"), list(st)))
 
 
 _sig("aslp_eesenctc_create", _i, C.POINTER(_H))
@@ -473,6 +512,16 @@ class Nnet:
         n = len(frame_num_utt)
         fl, ll = _flat(labels[:n])
         _ok(lib.aslp_nnet_train_step_warpctc(self.h, ctc.h, ptr(x), x.shape[0], x.shape[1], dim(x).stride, _i32arr(frame_num_utt), n, fl, ll))
+
+    def train_step_mse(self, mse, x, targets, frame_weights=None):
+        """Propagate -> Mse::Eval -> Backpropagate(+Update), all on the device; targets [rows x OutputDim()], frame_weights [rows] or None."""
+        _chk(x), _chk(targets)
+        if frame_weights is not None:
+            _chk(frame_weights)
+        if targets.shape[0] != x.shape[0] or targets.shape[1] != self.OutputDim():
+            raise ValueError("targets must be [rows x OutputDim()]")
+        _ok(lib.aslp_nnet_train_step_mse(self.h, mse.h, ptr(x), x.shape[0], x.shape[1], dim(x).stride, ptr(targets), dim(targets).stride,
+                                         ptr(frame_weights)))
 
     def TrainStepXent(self, xent, x, labels, frame_weights=None):
         """Propagate -> Xent::Eval -> Backpropagate(+Update), all on the device."""

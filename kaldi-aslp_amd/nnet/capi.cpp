@@ -1,4 +1,4 @@
-// capi.cpp -- C handle API (include/aslp_nnet.h) over Nnet / Xent.
+// capi.cpp -- C handle API (include/aslp_nnet.h) over Nnet / Xent / Mse.
 #include <cstdlib>
 #include <cstring>
 #include <memory>
@@ -23,6 +23,14 @@ struct aslp_nnet_s {
 };
 struct aslp_xent_s {
   Xent xent;
+};
+struct aslp_mse_s {
+  Mse mse;
+  CuVector ones;   // frame_weights == NULL
+  const CuVectorBase &Ones(int rows) {
+    if (ones.Dim() != rows) { ones.Resize(rows, kUndefined); ones.Set(1.0f); }
+    return ones;
+  }
 };
 struct aslp_matrix_randomizer_s {
   ~aslp_matrix_randomizer_s() { ReleaseStaged(); }
@@ -252,6 +260,44 @@ int aslp_nnet_train_step_xent(aslp_nnet_t n, aslp_xent_t x, const float *in, int
   CuSubVector fwv(const_cast<float *>(frame_weights), rows);
   if (n->nnet.LossInputIsPreSoftmax()) x->xent.EvalLabelsPreSoftmax(fwv, n->nnet.LossInput(), labels, n->nnet.LossDiff(rows), fw_max);
   else x->xent.EvalLabels(fwv, n->nnet.LossInput(), labels, n->nnet.LossDiff(rows), fw_max);
+  n->nnet.BackpropagateFromLossDiff();
+  API_END
+}
+
+int aslp_mse_create(aslp_mse_t *out) { API_BEGIN *out = new aslp_mse_s(); API_END }
+void aslp_mse_free(aslp_mse_t m) { delete m; }
+int aslp_mse_eval_batch(aslp_mse_t m, const float *net_out, int rows, int cols, int stride, const float *targets, int tgt_stride,
+                        const float *frame_weights, float *diff, int diff_stride) {
+  API_BEGIN
+  if (!m || !net_out || !targets || !diff || rows <= 0 || cols <= 0) ASLP_ERR << "aslp_mse_eval_batch: null argument or empty matrix";
+  // straight onto the kernel, into the caller's diff; the row sums stay parked inside m
+  CuSubMatrix y(const_cast<float *>(net_out), rows, cols, stride), t(const_cast<float *>(targets), rows, cols, tgt_stride);
+  CuSubMatrix d(diff, rows, cols, diff_stride);
+  if (frame_weights) {
+    CuSubVector fwv(const_cast<float *>(frame_weights), rows);
+    m->mse.EvalInto(NULL, &fwv, y, t, &d, 1.0f);
+  } else {
+    m->mse.EvalInto(NULL, &m->Ones(rows), y, t, &d, 1.0f);
+  }
+  API_END
+}
+int aslp_mse_report(aslp_mse_t m, char *buf, int buflen) { API_BEGIN CopyStr(m->mse.Report(), buf, buflen); API_END }
+int aslp_mse_get_stats(aslp_mse_t m, double stats[3]) { API_BEGIN m->mse.GetStats(stats); API_END }
+
+int aslp_nnet_train_step_mse(aslp_nnet_t n, aslp_mse_t m, const float *in, int rows, int cols, int stride, const float *targets, int tgt_stride,
+                             const float *frame_weights) {
+  API_BEGIN
+  if (!n || !m || !in || !targets) ASLP_ERR << "aslp_nnet_train_step_mse: null argument";
+  CuSubMatrix inm(const_cast<float *>(in), rows, cols, stride);
+  n->nnet.PropagateForLoss(inm, false);   // (Mse reads the network's output: no Softmax is left to the loss)
+  const CuMatrixBase &y = n->nnet.LossInput();
+  CuSubMatrix t(const_cast<float *>(targets), rows, y.NumCols(), tgt_stride);
+  if (frame_weights) {
+    CuSubVector fwv(const_cast<float *>(frame_weights), rows);
+    m->mse.EvalDevice(fwv, y, t, n->nnet.LossDiff(rows));
+  } else {
+    m->mse.EvalDevice(m->Ones(rows), y, t, n->nnet.LossDiff(rows));
+  }
   n->nnet.BackpropagateFromLossDiff();
   API_END
 }

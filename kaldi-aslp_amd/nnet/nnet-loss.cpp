@@ -230,28 +230,23 @@ std::string Xent::Report() {  // nnet-loss.cc:175-199
   return oss.str();
 }
 
-void Mse::Eval(const std::vector<BaseFloat> &frame_weights, const CuMatrixBase &net_out, const CuMatrixBase &target, CuMatrix *diff) {
-  // nnet-loss.cc:205-258
-  ASLP_ASSERT(net_out.NumCols() == target.NumCols());
-  ASLP_ASSERT(net_out.NumRows() == target.NumRows());
-  ASLP_ASSERT(net_out.NumRows() == (int)frame_weights.size());
+bool Mse::Fused() {
+  static const bool off = [] { const char *e = getenv("ASLP_MSE_FUSED"); return e != nullptr && e[0] == '0'; }();   // A/B switch
+  return !off;
+}
+
+// the frame count of a minibatch as the reference forms it: the weights summed in double, truncated (nnet-loss.cc:216-219)
+static int32 MseNumFrames(const std::vector<BaseFloat> &frame_weights) {
   double fsum = 0.0;
   for (BaseFloat w : frame_weights) fsum += w;
   ASLP_ASSERT(std::isfinite(fsum));
   int32 num_frames = fsum;
   ASLP_ASSERT(num_frames >= 0.0);
-  HostVector hv;
-  hv.data = frame_weights;
-  frame_weights_ = hv;
-  *diff = net_out;
-  diff->AddMat(-1.0, target);
-  diff->MulRowsVec(frame_weights_);
-  diff_pow_2_ = *diff;
-  diff_pow_2_.MulElements(diff_pow_2_);
-  diff_pow_2_.MulRowsVec(frame_weights_);
-  num_tgt_ = diff_pow_2_.NumCols();
-  double mean_square_error = 0.5 * diff_pow_2_.Sum();
-  ASLP_ASSERT(std::isfinite(mean_square_error));
+  return num_frames;
+}
+
+void Mse::AddBatch(double mean_square_error, double num_frames) {   // nnet-loss.cc:240-257
+  if (!std::isfinite(mean_square_error)) ASLP_ERR << "Mse: mean square error is not finite";
   loss_ += mean_square_error;
   frames_ += num_frames;
   static const int32 progress_step = 3600 * 100;
@@ -265,12 +260,142 @@ void Mse::Eval(const std::vector<BaseFloat> &frame_weights, const CuMatrixBase &
     loss_progress_ = 0.0;
   }
 }
+
+// ASLP_MSE_FUSED=0: the reference's op sequence, its sum read in every minibatch
+void Mse::EvalOps(const std::vector<BaseFloat> &frame_weights, const CuMatrixBase &net_out, const CuMatrixBase &target, CuMatrix *diff) {
+  const int32 num_frames = MseNumFrames(frame_weights);
+  HostVector hv;
+  hv.data = frame_weights;
+  frame_weights_ = hv;
+  *diff = net_out;
+  diff->AddMat(-1.0, target);
+  diff->MulRowsVec(frame_weights_);
+  CuMatrix diff_pow_2;
+  diff_pow_2 = *diff;
+  diff_pow_2.MulElements(diff_pow_2);
+  diff_pow_2.MulRowsVec(frame_weights_);
+  num_tgt_ = diff_pow_2.NumCols();
+  AddBatch(0.5 * diff_pow_2.Sum(), num_frames);
+}
+
+double *Mse::PendingRoom(int32 rows) {
+  static const int32 kMaxBatches = 32, kMaxRows = 1 << 16;
+  if (rows != pending_rows_) {
+    FlushPending();
+    pending_rows_ = rows;
+    pending_cap_ = std::max(1, std::min(kMaxBatches, kMaxRows / std::max(rows, 1)));
+    // (zeroed: the double behind a batch's rows is read by the sum launch also where no kernel wrote it)
+    if ((size_t)pending_.Dim() < (size_t)pending_cap_ * (rows + 1)) pending_.Resize(pending_cap_ * (rows + 1), kSetZero);
+  }
+  if (pending_batches_ == pending_cap_) FlushPending();
+  return pending_.Data() + (size_t)(pending_batches_++) * (rows + 1);
+}
+
+static const int32 kMseMaxSums = 1024;   // {sum, frames} pairs the device holds between two fetches
+void Mse::FlushPending() {
+  if (pending_batches_ == 0) return;
+  if (sums_.Dim() < 2 * kMseMaxSums) sums_.Resize(2 * kMseMaxSums, kSetZero);
+  if (num_sums_ + pending_batches_ > kMseMaxSums) DrainSums();
+  aslp_mse_batch_sums(pending_.Data(), pending_rows_, pending_batches_, sums_.Data() + 2 * (size_t)num_sums_);
+  CheckK();
+  num_sums_ += pending_batches_;
+  pending_batches_ = 0;
+}
+
+// the summed batches into the host accumulators, in batch order: what the reference does once per minibatch
+void Mse::DrainSums() {
+  if (num_sums_ == 0) return;
+  std::vector<double> h(2 * (size_t)num_sums_), frames(host_frames_.begin(), host_frames_.begin() + num_sums_);
+  DeviceToHost(h.data(), sums_.Data(), sizeof(double) * h.size());
+  host_frames_.erase(host_frames_.begin(), host_frames_.begin() + num_sums_);
+  num_sums_ = 0;
+  for (size_t b = 0; b < frames.size(); b++) AddBatch(0.5 * h[2 * b], frames[b] >= 0.0 ? frames[b] : h[2 * b + 1]);
+}
+
+void Mse::Fetch() {
+  FlushPending();
+  DrainSums();
+  parked_frames_ = 0.0;
+}
+
+void Mse::EvalInto(const std::vector<BaseFloat> *frame_weights, const CuVectorBase *frame_weights_dev, const CuMatrixBase &net_out,
+                   const CuMatrixBase &target, CuMatrixBase *diff, BaseFloat scale) {
+  ASLP_ASSERT(net_out.NumCols() == target.NumCols() && net_out.NumRows() == target.NumRows());
+  ASLP_ASSERT(net_out.NumCols() == diff->NumCols() && net_out.NumRows() == diff->NumRows());
+  const int32 rows = net_out.NumRows();
+  if (!Fused()) {
+    std::vector<BaseFloat> w;
+    if (frame_weights) {
+      w = *frame_weights;
+    } else {
+      ASLP_ASSERT(frame_weights_dev != NULL && frame_weights_dev->Dim() == rows);
+      w.resize(rows);
+      frame_weights_dev->CopyToHost(w.data());
+    }
+    ASLP_ASSERT(rows == (int32)w.size());
+    CuMatrix d;
+    EvalOps(w, net_out, target, &d);
+    if (scale != 1.0f) d.Scale(scale);
+    diff->CopyFromMat(d);
+    return;
+  }
+  double host_frames = -1.0;
+  const float *w_dev;
+  if (frame_weights) {
+    ASLP_ASSERT(rows == (int32)frame_weights->size());
+    host_frames = MseNumFrames(*frame_weights);
+    HostVector hv;
+    hv.data = *frame_weights;
+    frame_weights_ = hv;
+    w_dev = frame_weights_.Data();
+  } else {
+    ASLP_ASSERT(frame_weights_dev != NULL && frame_weights_dev->Dim() == rows);
+    w_dev = frame_weights_dev->Data();
+  }
+  num_tgt_ = net_out.NumCols();
+  // Is this the executor's loss diff (Nnet::LossDiff)?  No bound of |y - t| is known before the launch, so the kernel leaves the
+  // per-workgroup maxima of |diff| with the layer that reads it: its conversion (PlaneHolder::Of) then skips the maximum pass.
+  const S16DiffTarget t = s16_loss_diff_target();
+  aslp_planes_out po = aslp_planes_out();
+  PlaneSet *ps = nullptr;
+  if (t.planes && t.diff == diff->Data()) {
+    s16_loss_diff_target() = S16DiffTarget();
+    if (t.planes->ReserveParts()) { ps = t.planes; po.parts = ps->Parts(); }
+  }
+  double *room = PendingRoom(rows);
+  const int done = aslp_mse_eval_w(net_out.Data(), net_out.Dim(), target.Data(), target.Stride(), w_dev, scale, diff->Data(), diff->Stride(), room,
+                                   ps ? &po : nullptr, frame_weights ? nullptr : room + rows);
+  if (!done) pending_batches_--;
+  CheckK();
+  if (ps && po.nparts > 0) ps->TagParts(diff->Data(), po.nparts, t.epoch);
+  host_frames_.push_back(host_frames);
+  // progressive loss reporting (nnet-loss.cc:246-257) every 1h of frames: the threshold is known here, from the frames of the batches
+  // fetched so far and of those parked since (their rows where only the device knows the count)
+  static const int32 progress_step = 3600 * 100;
+  parked_frames_ += host_frames >= 0.0 ? host_frames : rows;
+  if (frames_progress_ + parked_frames_ > progress_step) Fetch();
+}
+
+void Mse::Eval(const std::vector<BaseFloat> &frame_weights, const CuMatrixBase &net_out, const CuMatrixBase &target, CuMatrix *diff) {
+  // nnet-loss.cc:205-258
+  ASLP_ASSERT(net_out.NumCols() == target.NumCols());
+  ASLP_ASSERT(net_out.NumRows() == target.NumRows());
+  ASLP_ASSERT(net_out.NumRows() == (int)frame_weights.size());
+  if (!Fused()) { EvalOps(frame_weights, net_out, target, diff); return; }
+  diff->Resize(net_out.NumRows(), net_out.NumCols(), kUndefined);
+  EvalInto(&frame_weights, NULL, net_out, target, diff, 1.0f);
+}
+void Mse::EvalDevice(const CuVectorBase &frame_weights, const CuMatrixBase &net_out, const CuMatrixBase &target, CuMatrix *diff) {
+  diff->Resize(net_out.NumRows(), net_out.NumCols(), kUndefined);
+  EvalInto(NULL, &frame_weights, net_out, target, diff, 1.0f);
+}
 void Mse::Eval(const std::vector<BaseFloat> &frame_weights, const CuMatrixBase &net_out, const Posterior &post, CuMatrix *diff) {
   ASLP_ASSERT(net_out.NumRows() == (int32)post.size());
   PosteriorToMatrix(post, net_out.NumCols(), &tgt_mat_);
   Eval(frame_weights, net_out, tgt_mat_, diff);
 }
 std::string Mse::Report() {  // nnet-loss.cc:277-290
+  Fetch();
   BaseFloat root_mean_square = sqrt(loss_ / frames_ / num_tgt_);
   std::ostringstream oss;
   oss << "AvgLoss: " << loss_ / frames_ << " (Mse), " << "[RMS " << root_mean_square << ", frames " << frames_ << "]" << std::endl;
@@ -306,6 +431,14 @@ void MultiTaskLoss::Eval(const std::vector<BaseFloat> &fw, const CuMatrixBase &n
   diff->Resize(num_frames, num_output);
   CuMatrix diff_aux;
   for (size_t i = 0; i < loss_vec_.size(); i++) {
+    Mse *mse = Mse::Fused() ? dynamic_cast<Mse *>(loss_vec_[i]) : nullptr;
+    if (mse) {   // straight into the task's column window, the task weight as the kernel's second rounding: no diff_aux, Scale, CopyFromMat
+      ASLP_ASSERT(num_frames == (int32)fw.size());
+      CuSubMatrix window = diff->ColRange(loss_dim_offset_[i], loss_dim_[i]);
+      mse->EvalInto(&fw, NULL, net_out.ColRange(loss_dim_offset_[i], loss_dim_[i]), tgt_mat_.ColRange(loss_dim_offset_[i], loss_dim_[i]), &window,
+                    loss_weights_[i]);
+      continue;
+    }
     loss_vec_[i]->Eval(fw, net_out.ColRange(loss_dim_offset_[i], loss_dim_[i]), tgt_mat_.ColRange(loss_dim_offset_[i], loss_dim_[i]), &diff_aux);
     diff_aux.Scale(loss_weights_[i]);
     diff->ColRange(loss_dim_offset_[i], loss_dim_[i]).CopyFromMat(diff_aux);

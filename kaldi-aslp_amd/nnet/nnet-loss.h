@@ -2,8 +2,11 @@
 // Same interface and Report() strings as src/aslp-nnet/nnet-loss.h:35-218 / nnet-loss.cc (the
 // bash schedulers grep these lines).  `Posterior` is hmm/posterior.h's type.
 // Difference in mechanism only: one fused kernel per Eval and NO blocking host reads per
-// minibatch -- the five statistics accumulate in device memory (double) and are fetched when
-// a report or the hourly progress line needs them.
+// minibatch -- Xent's five statistics accumulate in device memory (double), Mse's per-row loss
+// sums (and, where the weights are device-resident, its frame counts) are parked there batch by
+// batch, and both are fetched when a report or the hourly progress line needs them.  Mse keeps
+// the reference's op sequence behind ASLP_MSE_FUSED=0; MultiTaskLoss evaluates its tasks through
+// Xent and Mse, an mse task straight into its column window of the diff.
 #pragma once
 #include <string>
 #include <utility>
@@ -72,21 +75,44 @@ class Xent : public LossItf {
   int32 pending_rows_ = 0, pending_batches_ = 0, pending_cap_ = 0;
 };
 
+// One launch per Eval (aslp_mse_eval): the diff, the per-row loss sums and the per-workgroup maxima of |diff|.  The row sums are parked
+// batch after batch and reach loss_ -- 0.5 * sum per minibatch, in batch order, with the reference's progress line -- when AvgLoss(),
+// Report(), GetStats() or that progress line needs them (Fetch).  ASLP_MSE_FUSED=0 (read once per process): the reference's op sequence.
 class Mse : public LossItf {
  public:
   Mse() : frames_(0.0), loss_(0.0), frames_progress_(0.0), loss_progress_(0.0), num_tgt_(0) {}
   void Eval(const std::vector<BaseFloat> &frame_weights, const CuMatrixBase &net_out, const CuMatrixBase &target, CuMatrix *diff);
   void Eval(const std::vector<BaseFloat> &frame_weights, const CuMatrixBase &net_out, const Posterior &target, CuMatrix *diff);
   using LossItf::Eval;
+  // device-resident variant (no host data on the step path): weights and targets already on the GPU.  The minibatch's frame count
+  // (int32 of the weights' sum) is formed on the device and fetched with the losses.
+  void EvalDevice(const CuVectorBase &frame_weights, const CuMatrixBase &net_out, const CuMatrixBase &target, CuMatrix *diff);
+  // Eval / EvalDevice into a matrix the caller owns (not resized: a column window of MultiTaskLoss' diff, a C ABI caller's buffer), the
+  // diff multiplied by `scale` as a second rounding (MultiTaskLoss' task weight).  frame_weights == NULL: the device variant.
+  void EvalInto(const std::vector<BaseFloat> *frame_weights, const CuVectorBase *frame_weights_dev, const CuMatrixBase &net_out,
+                const CuMatrixBase &target, CuMatrixBase *diff, BaseFloat scale);
+  static bool Fused();   // the A/B switch
   std::string Report();
-  BaseFloat AvgLoss() { return loss_ / frames_; }
+  BaseFloat AvgLoss() { Fetch(); return loss_ / frames_; }
+  // raw accumulators {frames, loss, num_tgt}
+  void GetStats(double out[3]) { Fetch(); out[0] = frames_; out[1] = loss_; out[2] = num_tgt_; }
 
  private:
+  void EvalOps(const std::vector<BaseFloat> &frame_weights, const CuMatrixBase &net_out, const CuMatrixBase &target, CuMatrix *diff);
+  void AddBatch(double mean_square_error, double num_frames);   // one minibatch into the accumulators (nnet-loss.cc:240-257)
+  double *PendingRoom(int32 rows);   // room for the next batch's rows + 1 doubles
+  void FlushPending();               // parked rows -> one {sum, frames} pair per batch in sums_ (one launch)
+  void DrainSums();                  // ... -> the host accumulators, batch by batch (the one blocking read)
+  void Fetch();                      // both
   double frames_, loss_, frames_progress_, loss_progress_;
   std::vector<float> loss_vec_;
   CuVector frame_weights_;
-  CuMatrix tgt_mat_, diff_pow_2_;
+  CuMatrix tgt_mat_;
   int num_tgt_;
+  CuVectorD pending_, sums_;
+  int32 pending_rows_ = 0, pending_batches_ = 0, pending_cap_ = 0, num_sums_ = 0;
+  std::vector<double> host_frames_;   // per parked batch: the frame count the host formed, or -1 = the device's
+  double parked_frames_ = 0.0;        // of the parked batches: frames (rows where only the device knows) since the last Fetch
 };
 
 class MultiTaskLoss : public LossItf {

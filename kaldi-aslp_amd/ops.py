@@ -6,7 +6,7 @@ import ctypes as C
 
 import torch
 
-from ._lib import lib, MatrixDim, Dim3, GemmEpilogue, CtcComputeInfo, D3, check_error
+from ._lib import lib, MatrixDim, Dim3, GemmEpilogue, CtcComputeInfo, D3, PlanesOut, check_error
 
 
 def _chk(t, dtype=torch.float32):
@@ -344,6 +344,29 @@ def xent_sum_rowstats(rowstats, rows, batches, stats):
     """aslp_xent_sum_rowstats: `batches` blocks of `rows` per-row statistics added to the five accumulators, in order"""
     lib.aslp_xent_sum_rowstats(ptr(_chk(rowstats, torch.float64)), rows, batches, ptr(_chk(stats, torch.float64)))
     check_error()
+
+
+def mse_eval(net_out, targets, frame_weights, diff, row_loss, scale=1.0, parts=None, frames_out=None):
+    """aslp_mse_eval: diff = (net_out - targets) * w[row] (* scale), row_loss[row] (float64) = the row's sum of (e * e) * w[row]; parts
+    (256 floats, optional) receives one maximum of the finite |diff| per workgroup.  Returns (served, nparts); nothing raises, so that a
+    refusal (served == 0, the error string set) can be looked at: the caller reads last_error() / check_error()."""
+    for m in (net_out, targets, frame_weights, diff):
+        if m is not None:
+            _chk(m)
+    if row_loss is not None:
+        _chk(row_loss, torch.float64)
+    po = None
+    if parts is not None:
+        po = PlanesOut()
+        po.parts = ptr(_chk(parts))
+    d = dim(net_out) if net_out is not None else MatrixDim(0, 0, 0)
+    args = (ptr(net_out), d, ptr(targets), dim(targets).stride if targets is not None else 0, ptr(frame_weights), float(scale), ptr(diff),
+            dim(diff).stride if diff is not None else 0, ptr(row_loss), C.byref(po) if po is not None else None)
+    if frames_out is not None:
+        served = lib.aslp_mse_eval_w(*args, ptr(_chk(frames_out, torch.float64)))
+    else:
+        served = lib.aslp_mse_eval(*args)
+    return served, (po.nparts if po is not None else 0)
 
 
 def ctc_loss(acts, labels, input_lengths, want_grad=True):
