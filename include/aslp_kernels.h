@@ -450,6 +450,32 @@ int aslp_mse_eval_w(const float *net_out, MatrixDim d, const float *tgt, int tgt
 /* `batches` blocks of rows + 1 doubles each, consecutive in memory (a batch's row_loss and, behind it, its frames_out):
  * sums[2 b] = the sum of block b's rows in a fixed order, sums[2 b + 1] = the double behind them. */
 void aslp_mse_batch_sums(const double *pending, int rows, int batches, double *sums /* [2 x batches] */);
+/* Xent over up to 16 column blocks of in [d.rows x d.cols] in one launch: MultiTaskLoss' xent tasks over a <BlockSoftmax> output.
+ * Per (row, block), labels[row * n_blocks + block] being the target's column relative to the block (< 0 or >= cols: no target; a label is
+ * compared with column numbers only, never used as an address):
+ *   1. softmax != 0: y = the block's row softmax of the activations, bit for bit cudaF_softmax_reduce on that window (one wave per row up
+ *      to 512 columns; 256 threads on the scalar map or, where cols % 4 == 0 and the window's rows in `in` and `post_out` start on 16-byte
+ *      boundaries, on the 16-byte map).  softmax == 0: `in` holds y.
+ *   2. e = (y - onehot(label)) * (frame_weights[row] * tsum), tsum = 1 with a target and 0 without; rowstats[row][0..4] =
+ *      {w, correct * w, w log(y_label + 1e-20), w log(1 + 1e-20), w y_label} as aslp_xent_eval_rows leaves them (aslp_xent_sum_rowstats adds them up).
+ *   3. diff = e, or e * weight as a second rounding when weight != 1 (MultiTaskLoss' Scale).
+ *   4. mask != 0: diff *= (1 - s), s = the fp32 sum of the block's diff row (BlockSoftmax' backward), summed in a fixed order: a thread's
+ *      columns in rising order (lane + 64 k of the wave; tid + 256 k or, on the 16-byte map, 4 (tid + 256 j) .. + 3 of the workgroup),
+ *      the wave's butterfly (lane distances 32, 16, .. 1), then for a block wider than 512 the four waves in order.  No atomics.
+ *   5. post_out (nullable) receives y; diff_out->parts (nullable) one maximum of the finite |diff| per workgroup, diff_out->nparts =
+ *      min(rows, 256) of them: workgroup b serves rows b, b + nparts, ...
+ * Nothing is read at or behind a block's last column, nothing written outside the blocks' columns of diff / post_out.  Returns 1, or 0 =
+ * refused (a null pointer other than post_out / diff_out, a size <= 0, a stride below d.cols, n_blocks > 16, blocks that overlap or
+ * leave the matrix, a block wider than 8192): the error string is set and nothing is launched. */
+typedef struct aslp_xent_block_ {
+  int offset, cols;
+  float weight;
+  double *rowstats;   /* [rows x 5], device */
+} aslp_xent_block;
+int aslp_xent_blocks_supported(int block_cols);   /* 1 .. 8192 */
+int aslp_xent_blocks_eval(const float *in, MatrixDim d, const aslp_xent_block *blocks, int n_blocks, const int32_cuda *labels,
+                          const float *frame_weights, float *diff, int diff_stride, int softmax, int mask, float *post_out /* nullable */,
+                          int post_stride, aslp_planes_out *diff_out /* nullable */);
 /* cudaF_diff_sigmoid which also leaves the planes of its result: |e y (1 - y)| <= max |e| / 4 with max |e| from the n_parts per-workgroup
  * maxima the producer of e left (aslp_gemm_epilogue.cmax_parts).  The kernel stores the bound to out_planes->slot itself.  Returns 1 if the
  * planes were written, 0 if only eout was (operands not 16-byte aligned, no maxima). */

@@ -109,6 +109,33 @@ int aslp_mse_get_stats(aslp_mse_t m, double stats[3]);      /* frames, loss, num
 int aslp_nnet_train_step_mse(aslp_nnet_t n, aslp_mse_t m, const float *in, int rows, int cols, int stride, const float *targets,
                              int tgt_stride, const float *frame_weights);
 
+/* ---- MultiTaskLoss (nnet-loss.h:167-218) ----------------------------------------------------- */
+typedef struct aslp_multitask_s *aslp_multitask_t;
+/* spec: the reference's objective string, "multitask,<xent|mse>,<dim>,<weight>[,...]"; a malformed one is an error */
+int aslp_multitask_create(const char *spec, aslp_multitask_t *out);
+void aslp_multitask_free(aslp_multitask_t m);
+int aslp_multitask_num_tasks(aslp_multitask_t m);   /* -1: no handle */
+/* net_out, diff [rows x cols], cols = the sum of the task dims: all device.  labels [rows x number of xent tasks], row-major, in task
+ * order, relative to the task's first column, < 0 = no target (NULL only without an xent task).  targets: [rows x cols], read in the mse
+ * tasks' windows only (NULL only without an mse task).  frame_weights [rows], NULL = ones.  net_out holds the network's output (posteriors
+ * in the xent tasks' windows).  All xent tasks in one launch, an mse task in one each; nothing is read back before report / get_stats. */
+int aslp_multitask_eval_batch(aslp_multitask_t m, const float *net_out, int rows, int cols, int stride, const int32_t *labels,
+                              const float *targets, int tgt_stride, const float *frame_weights, float *diff, int diff_stride);
+int aslp_multitask_report(aslp_multitask_t m, char *buf, int buflen);   /* MultiTaskLoss::Report nnet-loss.cc:370 */
+int aslp_multitask_avg_loss(aslp_multitask_t m, float *avg_loss);
+/* kind: 0 xent, stats = frames, correct, loss, entropy, likelyhood; 1 mse, stats = frames, loss, num_tgt, 0, 0 */
+int aslp_multitask_get_stats(aslp_multitask_t m, int task, int *kind, double stats[5]);
+/* One whole training step with nothing on the host: Propagate -> MultiTaskLoss -> Backpropagate.  Where the network ends in a
+ * <BlockSoftmax> whose block dims are the task dims and every task is xent, the component is left to the loss kernel, which forms the
+ * posteriors and applies the component's backward mask (aslp_nnet_last_loss_fold tells). */
+int aslp_nnet_train_step_multitask(aslp_nnet_t n, aslp_multitask_t m, const float *in, int rows, int cols, int stride, const int32_t *labels,
+                                   const float *targets, int tgt_stride, const float *frame_weights);
+/* what the latest train step left to its loss kernel: 0 nothing, 1 the final Softmax, 2 the final BlockSoftmax */
+int aslp_nnet_last_loss_fold(aslp_nnet_t n);
+/* A/B switch (ASLP_MULTITASK_FUSED=0): off = the new entry points run the op sequence of MultiTaskLoss::Eval -- no fold, a dense target
+ * matrix from the labels, per task Eval, Scale, copy, the component's own backward */
+void aslp_multitask_fused(int on);
+
 /* ---- WarpCtc (aslp-nnet/warp-ctc.h:29-113) -------------------------------------------------- */
 typedef struct aslp_warpctc_s *aslp_warpctc_t;
 int aslp_warpctc_create(aslp_warpctc_t *out);

@@ -24,6 +24,11 @@ class PlanesOut(C.Structure):
     _fields_ = [("hi", C.c_void_p), ("lo", C.c_void_p), ("ld", C.c_int), ("slot", C.c_void_p), ("parts", C.c_void_p), ("nparts", C.c_int), ("planes_written", C.c_int)]
 
 
+class XentBlock(C.Structure):
+    """aslp_xent_block (include/aslp_kernels.h)"""
+    _fields_ = [("offset", C.c_int), ("cols", C.c_int), ("weight", C.c_float), ("rowstats", C.c_void_p)]
+
+
 class GemmEpilogue(C.Structure):
     _fields_ = [("bias", C.c_void_p), ("clip", C.c_float), ("W", C.c_void_p), ("ldw", C.c_int),
                 ("w_alpha", C.c_float), ("act_out", C.c_void_p), ("ld_act", C.c_int), ("act", C.c_int),
@@ -267,6 +272,9 @@ _sig("aslp_xent_sum_rowstats", None, _vp, _i, _i, _vp)
 _sig("aslp_mse_eval", _i, _vp, _md, _vp, _i, _vp, C.c_float, _vp, _i, _vp, C.POINTER(PlanesOut))
 _sig("aslp_mse_eval_w", _i, _vp, _md, _vp, _i, _vp, C.c_float, _vp, _i, _vp, C.POINTER(PlanesOut), _vp)
 _sig("aslp_mse_batch_sums", None, _vp, _i, _i, _vp)
+_sig("aslp_xent_blocks_supported", _i, _i)
+_sig("aslp_xent_blocks_eval", _i, _vp, _md, C.POINTER(XentBlock), _i, _vp, _vp, _vp, _i, _i, _i, _vp, _i, C.POINTER(PlanesOut))
+_sig("aslp_multitask_fused", None, _i)
 _sig("aslp_device_shared", None, _i)
 _sig("aslp_coop_convert", None, _i)
 _sig("aslp_softmax_xent_eval", None, _vp, _md, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _i)

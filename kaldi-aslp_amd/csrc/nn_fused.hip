@@ -1340,6 +1340,229 @@ __global__ void __launch_bounds__(256) mse_batch_sums_kernel(const double *pendi
   }
 }
 
+// ---- Xent over column blocks (MultiTaskLoss over BlockSoftmax) ---------------------------------------------------------------
+// aslp_xent_blocks_eval: per (row, block) the block's softmax, the labelled Xent diff and row statistics, the task weight and
+// BlockSoftmax' backward mask, in one launch.  The block table travels by value.
+constexpr int kXbMaxBlocks = 16;
+constexpr int kXbWaveCols = 512;   // up to here one wave holds a block's row (launch_softmax' first rung)
+struct XbArgs {
+  int n;
+  int off[kXbMaxBlocks], cols[kXbMaxBlocks];
+  float weight[kXbMaxBlocks];
+  double *rs[kXbMaxBlocks];
+  unsigned vec;    // bit b: block b's activations (and posteriors out) take the 16-byte map
+  unsigned dvec;   // bit b: ... and its diff rows allow 16-byte stores
+};
+struct XbShared {
+  float f[4];
+  float best[4];
+  int idx[4];
+};
+
+// One block of one row, held in the registers of NT threads from load to store: NT = 64, a wave (column lane + 64 k, the map of
+// softmax_rows_kernel<64>), or NT = 256, the workgroup (xent_rows_kernel's two maps).  The softmax is softmax_rows_kernel's arithmetic in
+// its order; diff, statistics and arg-max are those of xent_rows_kernel's label form.  The mask's row sum: a thread's slots in slot
+// order, the wave's butterfly, then (NT = 256) the four waves in order.  Returns the thread's largest finite |diff|.
+template <int NT, int PER, bool VEC>
+__device__ __forceinline__ float xb_block(const float *yr, const int cols, const int label, const float fw_r, const float weight, float *dr,
+                                          const bool dvec, float *pr, const bool softmax, const bool mask, double *rs, XbShared *sh) {
+#pragma clang fp contract(off)
+  static_assert(!VEC || (NT == 256 && PER % 4 == 0), "the 16-byte map is for whole-workgroup rows");
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int t = NT == 64 ? lane : (int)threadIdx.x;
+  auto col_of = [t](int k) { return VEC ? 4 * (t + (k >> 2) * NT) + (k & 3) : t + k * NT; };
+  float yv[PER];
+  if (VEC) {
+#pragma unroll
+    for (int k4 = 0; k4 < PER / 4; k4++) {
+      const int c = 4 * (t + k4 * NT);
+      if (c < cols) {
+        const float4 v4 = *reinterpret_cast<const float4 *>(yr + c);
+        yv[4 * k4] = v4.x; yv[4 * k4 + 1] = v4.y; yv[4 * k4 + 2] = v4.z; yv[4 * k4 + 3] = v4.w;
+      }
+    }
+  } else {
+#pragma unroll
+    for (int k = 0; k < PER; k++) {
+      const int c = t + k * NT;
+      if (c < cols) yv[k] = yr[c];
+    }
+  }
+  if (softmax) {
+    float m = -INFINITY;
+#pragma unroll
+    for (int k = 0; k < PER; k++)
+      if (col_of(k) < cols) m = fmaxf(m, yv[k]);
+    m = wave_max(m);
+    if (NT == 256) {
+      if (lane == 0) sh->f[w] = m;
+      __syncthreads();
+      m = fmaxf(fmaxf(fmaxf(sh->f[0], sh->f[1]), sh->f[2]), sh->f[3]);
+      __syncthreads();
+    }
+    float sum = 0.0f;
+#pragma unroll
+    for (int k = 0; k < PER; k++) {
+      if (col_of(k) < cols) {
+        yv[k] = expf(yv[k] - m);
+        sum += yv[k];
+      }
+    }
+    sum = wave_sum(sum);
+    if (NT == 256) {
+      if (lane == 0) sh->f[w] = sum;
+      __syncthreads();
+      sum = sh->f[0];
+      sum += sh->f[1]; sum += sh->f[2]; sum += sh->f[3];
+      __syncthreads();
+    }
+    const float inv = 1.0f / sum;
+#pragma unroll
+    for (int k = 0; k < PER; k++)
+      if (col_of(k) < cols) yv[k] *= inv;
+  }
+  if (pr) {
+    if (VEC) {
+#pragma unroll
+      for (int k4 = 0; k4 < PER / 4; k4++) {
+        const int c = 4 * (t + k4 * NT);
+        if (c < cols) *reinterpret_cast<float4 *>(pr + c) = make_float4(yv[4 * k4], yv[4 * k4 + 1], yv[4 * k4 + 2], yv[4 * k4 + 3]);
+      }
+    } else {
+#pragma unroll
+      for (int k = 0; k < PER; k++) {
+        const int c = t + k * NT;
+        if (c < cols) pr[c] = yv[k];
+      }
+    }
+  }
+  // the label is compared with column numbers only, never added to a pointer
+  const bool has_label = label >= 0 && label < cols;
+  const float wr = fw_r * (has_label ? 1.0f : 0.0f);
+  float ybest = -1e21f;
+  int yi = -1;
+  double xe = 0.0, en = 0.0, lk = 0.0;
+  float s = 0.0f;
+#pragma unroll
+  for (int k = 0; k < PER; k++) {
+    const int c = col_of(k);
+    if (c < cols) {
+      const float yy = yv[k], tt = (c == label ? 1.0f : 0.0f);
+      if (ybest < yy) { ybest = yy; yi = c; }
+      const float e = (yy - tt) * wr;
+      if (tt != 0.0f) {
+        xe += (double)(logf(yy + 1e-20f) * tt * wr);
+        en += (double)(logf(tt + 1e-20f) * tt * wr);
+        lk += (double)(yy * tt * wr);
+      }
+      yv[k] = weight != 1.0f ? e * weight : e;
+      s += yv[k];
+    }
+  }
+  if (mask) {
+    s = wave_sum(s);
+    if (NT == 256) {
+      if (lane == 0) sh->f[w] = s;
+      __syncthreads();
+      s = sh->f[0];
+      s += sh->f[1]; s += sh->f[2]; s += sh->f[3];
+      __syncthreads();
+    }
+    const float f = 1.0f - s;
+#pragma unroll
+    for (int k = 0; k < PER; k++)
+      if (col_of(k) < cols) yv[k] *= f;
+  }
+  float amax = 0.f;
+#pragma unroll
+  for (int k = 0; k < PER; k++)
+    if (col_of(k) < cols) {
+      const float a = fabsf(yv[k]);
+      amax = fmaxf(amax, a < 3.0e38f ? a : 0.f);
+    }
+  if (VEC && dvec) {
+#pragma unroll
+    for (int k4 = 0; k4 < PER / 4; k4++) {
+      const int c = 4 * (t + k4 * NT);
+      if (c < cols) *reinterpret_cast<float4 *>(dr + c) = make_float4(yv[4 * k4], yv[4 * k4 + 1], yv[4 * k4 + 2], yv[4 * k4 + 3]);
+    }
+  } else {
+#pragma unroll
+    for (int k = 0; k < PER; k++) {
+      const int c = col_of(k);
+      if (c < cols) dr[c] = yv[k];
+    }
+  }
+  // arg-max of the posteriors: the lowest index among equals, as xent_rows_kernel finds it
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float ov = __shfl_xor(ybest, o, 64);
+    const int oi = __shfl_xor(yi, o, 64);
+    if (ov > ybest || (ov == ybest && oi >= 0 && (yi < 0 || oi < yi))) { ybest = ov; yi = oi; }
+  }
+  if (NT == 256) {
+    if (lane == 0) { sh->best[w] = ybest; sh->idx[w] = yi; }
+    __syncthreads();
+    ybest = sh->best[0]; yi = sh->idx[0];
+#pragma unroll
+    for (int j = 1; j < 4; j++)
+      if (sh->best[j] > ybest || (sh->best[j] == ybest && sh->idx[j] >= 0 && (yi < 0 || sh->idx[j] < yi))) { ybest = sh->best[j]; yi = sh->idx[j]; }
+    __syncthreads();
+  }
+  const int ti = has_label ? label : 0;
+  // a label target has one non-zero term, in the thread that holds the label's column: its three sums are the row's
+  const bool mine = has_label && (VEC ? ((label >> 2) & (NT - 1)) == t : (label & (NT - 1)) == t);
+  if (mine) { rs[2] = xe; rs[3] = en; rs[4] = lk; }
+  if (t == 0) {
+    rs[0] = (double)wr;
+    rs[1] = (double)wr * (yi == ti ? 1.0 : 0.0);
+    if (!has_label) { rs[2] = 0.0; rs[3] = 0.0; rs[4] = 0.0; }
+  }
+  return amax;
+}
+
+// One workgroup per row, workgroup b of the g <= 256 takes rows b, b + g, ...  Blocks wider than 512 columns take the whole workgroup,
+// one after the other (PER: the slots of the widest); then wave w serves the narrower blocks w, w + 4, ... of those, no barrier between
+// them.  parts[b] (nullable): the largest finite |diff| of the workgroup's rows.
+template <int PER>
+__global__ void __launch_bounds__(256) xent_blocks_kernel(const float *in, int ldi, XbArgs a, const int32_t *labels, const float *fw, float *diff, int ldd,
+                                                          int rows, int softmax, int mask, float *post, int ldp, float *parts) {
+  __shared__ XbShared sh;
+  __shared__ float red[kPanelWaves];
+  const int wave = threadIdx.x >> 6;
+  float amax = 0.f;
+  for (int r = blockIdx.x; r < rows; r += gridDim.x) {
+    const float fw_r = fw[r];
+    const float *ir = in + (long)r * ldi;
+    float *dr = diff + (long)r * ldd;
+    float *pr = post != nullptr ? post + (long)r * ldp : nullptr;
+    const int32_t *lr = labels + (long)r * a.n;
+    for (int b = 0; b < a.n; b++) {   // (uniform: the table is the launch's)
+      if (a.cols[b] <= kXbWaveCols) continue;
+      double *rs = a.rs[b] + (long)r * 5;
+      float *pb = pr != nullptr ? pr + a.off[b] : nullptr;
+      float m;
+      if ((a.vec >> b) & 1u)
+        m = xb_block<256, PER, true>(ir + a.off[b], a.cols[b], lr[b], fw_r, a.weight[b], dr + a.off[b], ((a.dvec >> b) & 1u) != 0, pb, softmax != 0, mask != 0, rs, &sh);
+      else
+        m = xb_block<256, PER, false>(ir + a.off[b], a.cols[b], lr[b], fw_r, a.weight[b], dr + a.off[b], false, pb, softmax != 0, mask != 0, rs, &sh);
+      amax = fmaxf(amax, m);
+    }
+    int narrow = 0;
+    for (int b = 0; b < a.n; b++) {
+      if (a.cols[b] > kXbWaveCols) continue;
+      if ((narrow++ & 3) != wave) continue;
+      const float m = xb_block<64, kXbWaveCols / 64, false>(ir + a.off[b], a.cols[b], lr[b], fw_r, a.weight[b], dr + a.off[b], false,
+                                                             pr != nullptr ? pr + a.off[b] : nullptr, softmax != 0, mask != 0, a.rs[b] + (long)r * 5, nullptr);
+      amax = fmaxf(amax, m);
+    }
+  }
+  if (parts != nullptr) {   // (uniform)
+    amax = wg_max(amax, red);
+    if (threadIdx.x == 0) parts[blockIdx.x] = amax;
+  }
+}
+
 }  // namespace
 
 static bool g_coop_convert_on = true;   // aslp_coop_convert (tests: the two-launch conversion as the reference)
@@ -1708,6 +1931,58 @@ void aslp_mse_batch_sums(const double *pending, int rows, int batches, double *s
   if (!pending || !sums || rows <= 0 || batches <= 0) return;
   hipLaunchKernelGGL(mse_batch_sums_kernel, dim3(batches), dim3(256), 0, cur_stream(), pending, rows, sums);
   check_launch("mse_batch_sums");
+}
+
+// Xent over up to 16 column blocks of one matrix in one launch (xent_blocks_kernel above).  0 = refused, nothing launched.
+int aslp_xent_blocks_supported(int block_cols) { return block_cols >= 1 && block_cols <= 256 * kXentPerThread; }
+int aslp_xent_blocks_eval(const float *in, MatrixDim d, const aslp_xent_block *blocks, int n_blocks, const int32_cuda *labels,
+                          const float *frame_weights, float *diff, int diff_stride, int softmax, int mask, float *post_out, int post_stride,
+                          aslp_planes_out *diff_out) {
+  if (diff_out) { diff_out->nparts = 0; diff_out->planes_written = 0; }
+  if (!in || !blocks || !labels || !frame_weights || !diff) { set_error("aslp_xent_blocks_eval: null argument"); return 0; }
+  if (d.rows <= 0 || d.cols <= 0 || d.stride < d.cols || diff_stride < d.cols || (post_out && post_stride < d.cols)) {
+    set_error("aslp_xent_blocks_eval: sizes must be positive and no stride smaller than the number of columns");
+    return 0;
+  }
+  if (n_blocks <= 0 || n_blocks > kXbMaxBlocks) { set_error("aslp_xent_blocks_eval: 1 .. 16 blocks"); return 0; }
+  XbArgs a;
+  a.n = n_blocks;
+  a.vec = a.dvec = 0u;
+  int widest = 0;
+  for (int b = 0; b < n_blocks; b++) {
+    const aslp_xent_block &k = blocks[b];
+    if (!k.rowstats) { set_error("aslp_xent_blocks_eval: a block without room for its row statistics"); return 0; }
+    if (!aslp_xent_blocks_supported(k.cols)) { set_error("aslp_xent_blocks_eval: a block must be 1 .. 8192 columns wide"); return 0; }
+    if (k.offset < 0 || k.offset > d.cols - k.cols) { set_error("aslp_xent_blocks_eval: a block outside the matrix"); return 0; }
+    for (int o = 0; o < b; o++)
+      if (k.offset < blocks[o].offset + blocks[o].cols && blocks[o].offset < k.offset + k.cols) {
+        set_error("aslp_xent_blocks_eval: overlapping blocks");
+        return 0;
+      }
+    a.off[b] = k.offset; a.cols[b] = k.cols; a.weight[b] = k.weight; a.rs[b] = k.rowstats;
+    if (k.cols > kXbWaveCols) {
+      widest = std::max(widest, k.cols);
+      // launch_softmax' rule for the window: its rows and the posteriors' on 16-byte boundaries
+      const bool vec = softmax_rows_vec_ok(k.cols) && (d.stride & 3) == 0 && aligned16(in + k.offset) &&
+                       (!post_out || ((post_stride & 3) == 0 && aligned16(post_out + k.offset)));
+      if (vec) a.vec |= 1u << b;
+      if (vec && (diff_stride & 3) == 0 && aligned16(diff + k.offset)) a.dvec |= 1u << b;
+    }
+  }
+  float *parts = diff_out ? diff_out->parts : nullptr;
+  const int g = std::min(d.rows, kS16ConvParts);
+  const int per = (widest + 255) / 256;
+#define XB_LAUNCH(P)                                                                                                                          \
+  hipLaunchKernelGGL((xent_blocks_kernel<P>), dim3(g), dim3(256), 0, cur_stream(), in, d.stride, a, labels, frame_weights, diff, diff_stride, \
+                     d.rows, softmax, mask, post_out, post_stride, parts)
+  if (per <= 4) XB_LAUNCH(4);
+  else if (per <= 8) XB_LAUNCH(8);
+  else if (per <= 16) XB_LAUNCH(16);
+  else XB_LAUNCH(32);
+#undef XB_LAUNCH
+  check_launch("xent_blocks_eval");
+  if (parts) diff_out->nparts = g;
+  return 1;
 }
 
 }  // extern "C"

@@ -58,6 +58,15 @@ _sig("aslp_mse_eval_batch", _i, _H, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _i)
 _sig("aslp_mse_report", _i, _H, C.c_char_p, _i)
 _sig("aslp_mse_get_stats", _i, _H, C.POINTER(C.c_double))
 _sig("aslp_nnet_train_step_mse", _i, _H, _H, _vp, _i, _i, _i, _vp, _i, _vp)
+_sig("aslp_multitask_create", _i, C.c_char_p, C.POINTER(_H))
+_sig("aslp_multitask_free", None, _H)
+_sig("aslp_multitask_num_tasks", _i, _H)
+_sig("aslp_multitask_eval_batch", _i, _H, _vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _i)
+_sig("aslp_multitask_report", _i, _H, C.c_char_p, _i)
+_sig("aslp_multitask_avg_loss", _i, _H, C.POINTER(_f))
+_sig("aslp_multitask_get_stats", _i, _H, _i, C.POINTER(_i), C.POINTER(C.c_double))
+_sig("aslp_nnet_train_step_multitask", _i, _H, _H, _vp, _i, _i, _i, _vp, _vp, _i, _vp)
+_sig("aslp_nnet_last_loss_fold", _i, _H)
 _i32p = C.POINTER(C.c_int32)
 _sig("aslp_warpctc_create", _i, C.POINTER(_H))
 _sig("aslp_warpctc_free", None, _H)
@@ -132,6 +141,56 @@ class Mse:
         st = (C.c_double * 3)()
         _ok(lib.aslp_mse_get_stats(self.h, st))
         return dict(zip(("frames", "loss", "num_tgt"), list(st)))
+
+
+class MultiTaskLoss:
+    """MultiTaskLoss (nnet-loss.h:167-218) from the reference's objective string, e.g. "multitask,xent,3000,1.0,xent,40,0.3": all xent
+    tasks in one launch, an mse task in one each, nothing read back until Report() / AvgLoss() / GetStats()"""
+
+    def __init__(self, spec):
+        self.h = _H()
+        _ok(lib.aslp_multitask_create(spec.encode(), C.byref(self.h)))
+
+    def __del__(self):
+        if getattr(self, "h", None) and lib is not None:
+            lib.aslp_multitask_free(self.h)
+            self.h = None
+
+    def NumTasks(self):
+        return lib.aslp_multitask_num_tasks(self.h)
+
+    def Eval(self, frame_weights, net_out, diff, labels=None, targets=None):
+        """net_out (the network's output), diff [rows x sum of the task dims]; labels int32 [rows x number of xent tasks], relative to the
+        task, < 0 = no target; targets [rows x cols], read in the mse tasks' windows; frame_weights [rows] or None = ones"""
+        _chk(net_out), _chk(diff)
+        if frame_weights is not None:
+            _chk(frame_weights)
+        if labels is not None:
+            _chk(labels, torch.int32)
+        if targets is not None:
+            _chk(targets)
+        if diff.shape != net_out.shape or (targets is not None and targets.shape != net_out.shape):
+            raise ValueError("net_out, targets and diff must have one shape")
+        _ok(lib.aslp_multitask_eval_batch(self.h, ptr(net_out), net_out.shape[0], net_out.shape[1], dim(net_out).stride, ptr(labels),
+                                          ptr(targets), dim(targets).stride if targets is not None else 0, ptr(frame_weights), ptr(diff),
+                                          dim(diff).stride))
+
+    def Report(self):
+        buf = C.create_string_buffer(8192)
+        _ok(lib.aslp_multitask_report(self.h, buf, 8192))
+        return buf.value.decode()
+
+    def AvgLoss(self):
+        v = _f()
+        _ok(lib.aslp_multitask_avg_loss(self.h, C.byref(v)))
+        return v.value
+
+    def GetStats(self, task):
+        st, kind = (C.c_double * 5)(), _i()
+        _ok(lib.aslp_multitask_get_stats(self.h, task, C.byref(kind), st))
+        if kind.value == 0:
+            return dict(zip(("frames", "correct", "loss", "entropy", "likelyhood"), list(st)), kind="xent")
+        return dict(zip(("frames", "loss", "num_tgt"), list(st)[:3]), kind="mse")
 
 
 _sig("aslp_eesenctc_create", _i, C.POINTER(_H))
@@ -522,6 +581,25 @@ class Nnet:
             raise ValueError("targets must be [rows x OutputDim()]")
         _ok(lib.aslp_nnet_train_step_mse(self.h, mse.h, ptr(x), x.shape[0], x.shape[1], dim(x).stride, ptr(targets), dim(targets).stride,
                                          ptr(frame_weights)))
+
+    def train_step_multitask(self, loss, x, labels=None, targets=None, frame_weights=None):
+        """Propagate -> MultiTaskLoss -> Backpropagate(+Update), all on the device; labels int32 [rows x number of xent tasks], targets
+        [rows x OutputDim()] (mse tasks), frame_weights [rows] or None.  A final <BlockSoftmax> whose blocks are the (all xent) tasks is
+        left to the loss kernel: LastLossFold() == 2."""
+        _chk(x)
+        for t, dt in ((labels, torch.int32), (targets, torch.float32), (frame_weights, torch.float32)):
+            if t is not None:
+                _chk(t, dt)
+        if labels is not None and labels.shape[0] != x.shape[0]:
+            raise ValueError("labels must be [rows x number of xent tasks]")
+        if targets is not None and (targets.shape[0] != x.shape[0] or targets.shape[1] != self.OutputDim()):
+            raise ValueError("targets must be [rows x OutputDim()]")
+        _ok(lib.aslp_nnet_train_step_multitask(self.h, loss.h, ptr(x), x.shape[0], x.shape[1], dim(x).stride, ptr(labels), ptr(targets),
+                                               dim(targets).stride if targets is not None else 0, ptr(frame_weights)))
+
+    def LastLossFold(self):
+        """what the latest train step left to its loss kernel: 0 nothing, 1 the final Softmax, 2 the final BlockSoftmax"""
+        return lib.aslp_nnet_last_loss_fold(self.h)
 
     def TrainStepXent(self, xent, x, labels, frame_weights=None):
         """Propagate -> Xent::Eval -> Backpropagate(+Update), all on the device."""

@@ -1,4 +1,4 @@
-// capi.cpp -- C handle API (include/aslp_nnet.h) over Nnet / Xent / Mse.
+// capi.cpp -- C handle API (include/aslp_nnet.h) over Nnet / Xent / Mse / MultiTaskLoss.
 #include <cstdlib>
 #include <cstring>
 #include <memory>
@@ -26,6 +26,14 @@ struct aslp_xent_s {
 };
 struct aslp_mse_s {
   Mse mse;
+  CuVector ones;   // frame_weights == NULL
+  const CuVectorBase &Ones(int rows) {
+    if (ones.Dim() != rows) { ones.Resize(rows, kUndefined); ones.Set(1.0f); }
+    return ones;
+  }
+};
+struct aslp_multitask_s {
+  MultiTaskLoss loss;
   CuVector ones;   // frame_weights == NULL
   const CuVectorBase &Ones(int rows) {
     if (ones.Dim() != rows) { ones.Resize(rows, kUndefined); ones.Set(1.0f); }
@@ -298,6 +306,68 @@ int aslp_nnet_train_step_mse(aslp_nnet_t n, aslp_mse_t m, const float *in, int r
   } else {
     m->mse.EvalDevice(m->Ones(rows), y, t, n->nnet.LossDiff(rows));
   }
+  n->nnet.BackpropagateFromLossDiff();
+  API_END
+}
+
+int aslp_multitask_create(const char *spec, aslp_multitask_t *out) {
+  API_BEGIN
+  if (!spec || !spec[0] || !out) ASLP_ERR << "aslp_multitask_create: null argument or empty spec";
+  aslp_multitask_s *h = new aslp_multitask_s();
+  try { h->loss.InitFromString(spec); } catch (...) { delete h; throw; }
+  *out = h;
+  API_END
+}
+void aslp_multitask_free(aslp_multitask_t m) { delete m; }
+int aslp_multitask_num_tasks(aslp_multitask_t m) { return m ? m->loss.NumTasks() : -1; }
+int aslp_multitask_eval_batch(aslp_multitask_t m, const float *net_out, int rows, int cols, int stride, const int32_t *labels,
+                              const float *targets, int tgt_stride, const float *frame_weights, float *diff, int diff_stride) {
+  API_BEGIN
+  if (!m || !net_out || !diff || rows <= 0 || cols <= 0) ASLP_ERR << "aslp_multitask_eval_batch: null argument or empty matrix";
+  if (cols != m->loss.TotalDim()) ASLP_ERR << "aslp_multitask_eval_batch: " << cols << " columns, the task dims sum to " << m->loss.TotalDim();
+  if (stride < cols || diff_stride < cols || (targets && tgt_stride < cols)) ASLP_ERR << "aslp_multitask_eval_batch: a stride below the number of columns";
+  CuSubMatrix y(const_cast<float *>(net_out), rows, cols, stride), d(diff, rows, cols, diff_stride);
+  CuSubMatrix t(const_cast<float *>(targets), rows, cols, tgt_stride);
+  if (frame_weights) {
+    CuSubVector fwv(const_cast<float *>(frame_weights), rows);
+    m->loss.EvalDevice(fwv, y, false, labels, targets ? &t : NULL, &d);
+  } else {
+    m->loss.EvalDevice(m->Ones(rows), y, false, labels, targets ? &t : NULL, &d);
+  }
+  API_END
+}
+int aslp_multitask_report(aslp_multitask_t m, char *buf, int buflen) { API_BEGIN CopyStr(m->loss.Report(), buf, buflen); API_END }
+int aslp_multitask_avg_loss(aslp_multitask_t m, float *avg_loss) { API_BEGIN *avg_loss = m->loss.AvgLoss(); API_END }
+int aslp_multitask_get_stats(aslp_multitask_t m, int task, int *kind, double stats[5]) {
+  API_BEGIN
+  if (!m || task < 0 || task >= m->loss.NumTasks()) ASLP_ERR << "aslp_multitask_get_stats: no such task";
+  if (kind) *kind = (int)m->loss.Kind(task);
+  m->loss.GetTaskStats(task, stats);
+  API_END
+}
+void aslp_multitask_fused(int on) { MultiTaskLoss::SetFused(on != 0); }
+int aslp_nnet_last_loss_fold(aslp_nnet_t n) { return n ? n->nnet.LastLossFold() : -1; }
+
+int aslp_nnet_train_step_multitask(aslp_nnet_t n, aslp_multitask_t m, const float *in, int rows, int cols, int stride, const int32_t *labels,
+                                   const float *targets, int tgt_stride, const float *frame_weights) {
+  API_BEGIN
+  if (!n || !m || !in) ASLP_ERR << "aslp_nnet_train_step_multitask: null argument";
+  CuSubMatrix inm(const_cast<float *>(in), rows, cols, stride);
+  // the BlockSoftmax is left to the loss only where the loss' tasks are its blocks, all of them xent
+  bool fold = MultiTaskLoss::Fused() && m->loss.NumXentTasks() == m->loss.NumTasks();
+  if (fold) {
+    const std::vector<int32> *dims = n->nnet.FinalBlockSoftmaxDims();
+    fold = dims != NULL && (int32)dims->size() == m->loss.NumTasks();
+    for (int32 i = 0; fold && i < m->loss.NumTasks(); i++) fold = (*dims)[i] == m->loss.Dim(i);
+  }
+  n->nnet.PropagateForLoss(inm, false, fold);
+  const CuMatrixBase &y = n->nnet.LossInput();
+  if (y.NumCols() != m->loss.TotalDim()) ASLP_ERR << "aslp_nnet_train_step_multitask: the network has " << y.NumCols() << " outputs, the task dims sum to " << m->loss.TotalDim();
+  CuSubMatrix t(const_cast<float *>(targets), rows, y.NumCols(), tgt_stride);
+  const CuVectorBase *fw = &m->Ones(rows);
+  CuSubVector fwv(const_cast<float *>(frame_weights), rows);
+  if (frame_weights) fw = &fwv;
+  m->loss.EvalDevice(*fw, y, n->nnet.LossInputIsPreBlockSoftmax(), labels, targets ? &t : NULL, n->nnet.LossDiff(rows));
   n->nnet.BackpropagateFromLossDiff();
   API_END
 }

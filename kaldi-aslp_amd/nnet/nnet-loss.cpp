@@ -429,6 +429,10 @@ void MultiTaskLoss::Eval(const std::vector<BaseFloat> &fw, const CuMatrixBase &n
   ASLP_ASSERT(num_output == loss_dim_offset_.back());
   PosteriorToMatrix(post, num_output, &tgt_mat_);
   diff->Resize(num_frames, num_output);
+  EvalTasks(fw, net_out, diff);
+}
+void MultiTaskLoss::EvalTasks(const std::vector<BaseFloat> &fw, const CuMatrixBase &net_out, CuMatrixBase *diff) {
+  const int32 num_frames = net_out.NumRows();
   CuMatrix diff_aux;
   for (size_t i = 0; i < loss_vec_.size(); i++) {
     Mse *mse = Mse::Fused() ? dynamic_cast<Mse *>(loss_vec_[i]) : nullptr;
@@ -444,6 +448,103 @@ void MultiTaskLoss::Eval(const std::vector<BaseFloat> &fw, const CuMatrixBase &n
     diff->ColRange(loss_dim_offset_[i], loss_dim_[i]).CopyFromMat(diff_aux);
   }
 }
+static int g_multitask_fused = -1;   // -1: not asked yet (the environment decides)
+bool MultiTaskLoss::Fused() {
+  if (g_multitask_fused < 0) {
+    const char *e = getenv("ASLP_MULTITASK_FUSED");
+    g_multitask_fused = (e != nullptr && e[0] == '0') ? 0 : 1;
+  }
+  return g_multitask_fused != 0;
+}
+void MultiTaskLoss::SetFused(bool on) { g_multitask_fused = on ? 1 : 0; }
+
+int32 MultiTaskLoss::NumXentTasks() const {
+  int32 n = 0;
+  for (int32 i = 0; i < NumTasks(); i++) n += Kind(i) == kXentTask ? 1 : 0;
+  return n;
+}
+MultiTaskLoss::TaskKind MultiTaskLoss::Kind(int32 task) const { return dynamic_cast<const Xent *>(loss_vec_[task]) ? kXentTask : kMseTask; }
+void MultiTaskLoss::GetTaskStats(int32 task, double out[5]) {
+  ASLP_ASSERT(task >= 0 && task < NumTasks());
+  for (int k = 0; k < 5; k++) out[k] = 0.0;
+  if (Xent *x = dynamic_cast<Xent *>(loss_vec_[task])) x->GetStats(out);
+  else dynamic_cast<Mse *>(loss_vec_[task])->GetStats(out);
+}
+
+void Xent::AddRowStats(const double *rowstats, int32 rows) {
+  FlushPending();   // (the accumulators take the batches in evaluation order)
+  aslp_xent_sum_rowstats(rowstats, rows, 1, stats_.Data());
+}
+
+void MultiTaskLoss::EvalDevice(const CuVectorBase &fw, const CuMatrixBase &in, bool pre_block_softmax, const int32 *labels_dev,
+                               const CuMatrixBase *dense_targets, CuMatrixBase *diff) {
+  const int32 rows = in.NumRows(), cols = in.NumCols(), num_tasks = NumTasks(), num_xent = NumXentTasks();
+  ASLP_ASSERT(rows > 0 && cols == TotalDim() && fw.Dim() == rows);
+  ASLP_ASSERT(diff != NULL && diff->NumRows() == rows && diff->NumCols() == cols);
+  if (num_xent > 0 && labels_dev == NULL) ASLP_ERR << "MultiTaskLoss: an xent task needs labels";
+  if (num_xent < num_tasks && (dense_targets == NULL || dense_targets->NumRows() != rows || dense_targets->NumCols() != cols))
+    ASLP_ERR << "MultiTaskLoss: an mse task needs dense targets [" << rows << " x " << cols << "]";
+  if (pre_block_softmax && (num_xent < num_tasks || !Fused())) ASLP_ERR << "MultiTaskLoss: only xent tasks on the fused route take a BlockSoftmax' input";
+  // (the executor's offer to leave the diff's planes or maxima is for a loss that writes the whole diff: not taken, and not left for a
+  //  task that writes a window of it)
+  s16_loss_diff_target() = S16DiffTarget();
+  if (!Fused()) {
+    // today's op sequence: the dense target matrix scattered from the labels, then the tasks one by one as in Eval(Posterior)
+    std::vector<int32> labels((size_t)rows * num_xent);
+    if (num_xent > 0) DeviceToHost(labels.data(), labels_dev, sizeof(int32) * labels.size());
+    Posterior post(rows);
+    for (int32 i = 0, x = 0; i < num_tasks; i++) {
+      if (Kind(i) != kXentTask) continue;
+      for (int32 t = 0; t < rows; t++) {
+        const int32 l = labels[(size_t)t * num_xent + x];
+        if (l >= 0 && l < loss_dim_[i]) post[t].push_back(std::make_pair(loss_dim_offset_[i] + l, 1.0f));
+      }
+      x++;
+    }
+    PosteriorToMatrix(post, cols, &tgt_mat_);
+    for (int32 i = 0; i < num_tasks; i++)
+      if (Kind(i) == kMseTask) tgt_mat_.ColRange(loss_dim_offset_[i], loss_dim_[i]).CopyFromMat(dense_targets->ColRange(loss_dim_offset_[i], loss_dim_[i]));
+    std::vector<BaseFloat> w(rows);
+    fw.CopyToHost(w.data());
+    EvalTasks(w, in, diff);
+    return;
+  }
+  for (int32 i = 0; i < num_tasks; i++)
+    if (Kind(i) == kXentTask && !aslp_xent_blocks_supported(loss_dim_[i])) ASLP_ERR << "MultiTaskLoss: unsupported xent task width " << loss_dim_[i];
+  if (num_xent > 16) ASLP_ERR << "MultiTaskLoss: more than 16 xent tasks";
+  if (num_xent > 0) {
+    std::vector<aslp_xent_block> blocks;
+    std::vector<Xent *> xents;
+    bool own_room = false;
+    for (int32 i = 0; i < num_tasks; i++) {
+      Xent *x = dynamic_cast<Xent *>(loss_vec_[i]);
+      if (!x) continue;
+      aslp_xent_block b = {loss_dim_offset_[i], loss_dim_[i], loss_weights_[i], x->DeferredRoom(rows)};
+      if (!b.rowstats) own_room = true;
+      blocks.push_back(b);
+      xents.push_back(x);
+    }
+    if (own_room) {   // too many rows to defer: the statistics are summed right behind the launch
+      if ((size_t)rowstats_tmp_.Dim() < (size_t)rows * 5 * blocks.size()) rowstats_tmp_.Resize(rows * 5 * (int32)blocks.size(), kUndefined);
+      for (size_t k = 0; k < blocks.size(); k++) blocks[k].rowstats = rowstats_tmp_.Data() + k * (size_t)rows * 5;
+    }
+    aslp_xent_blocks_eval(in.Data(), in.Dim(), blocks.data(), (int)blocks.size(), labels_dev, fw.Data(), diff->Data(), diff->Stride(),
+                          pre_block_softmax ? 1 : 0, pre_block_softmax ? 1 : 0, nullptr, 0, nullptr);
+    CheckK();
+    for (size_t k = 0; k < xents.size(); k++) {
+      if (own_room) xents[k]->AddRowStats(blocks[k].rowstats, rows);
+      xents[k]->EvalDone(rows);
+    }
+  }
+  for (int32 i = 0; i < num_tasks; i++) {
+    Mse *mse = dynamic_cast<Mse *>(loss_vec_[i]);
+    if (!mse) continue;
+    CuSubMatrix window = diff->ColRange(loss_dim_offset_[i], loss_dim_[i]);
+    mse->EvalInto(NULL, &fw, in.ColRange(loss_dim_offset_[i], loss_dim_[i]), dense_targets->ColRange(loss_dim_offset_[i], loss_dim_[i]), &window,
+                  loss_weights_[i]);
+  }
+}
+
 std::string MultiTaskLoss::Report() {  // nnet-loss.cc:370-393
   BaseFloat overall_loss = AvgLoss();
   std::ostringstream oss;

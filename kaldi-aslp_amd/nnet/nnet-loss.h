@@ -6,7 +6,8 @@
 // sums (and, where the weights are device-resident, its frame counts) are parked there batch by
 // batch, and both are fetched when a report or the hourly progress line needs them.  Mse keeps
 // the reference's op sequence behind ASLP_MSE_FUSED=0; MultiTaskLoss evaluates its tasks through
-// Xent and Mse, an mse task straight into its column window of the diff.
+// Xent and Mse, an mse task straight into its column window of the diff; its device-resident form (EvalDevice) sends all xent tasks
+// through one launch, aslp_xent_blocks_eval, which also stands in for a final <BlockSoftmax> (ASLP_MULTITASK_FUSED=0: the op sequence).
 #pragma once
 #include <string>
 #include <utility>
@@ -54,6 +55,12 @@ class Xent : public LossItf {
   BaseFloat AvgLoss() { Fetch(); return (loss_ - entropy_) / frames_; }
   // raw accumulators {frames, correct, loss, entropy, likelyhood}
   void GetStats(double out[5]) { Fetch(); out[0] = frames_; out[1] = correct_; out[2] = loss_; out[3] = entropy_; out[4] = likelyhood_; }
+  // For a kernel that evaluates this Xent beside others in one launch (MultiTaskLoss::EvalDevice): DeferredRoom gives the room for the
+  // batch's [rows x 5] row statistics (NULL: too many rows to defer -- the caller keeps them itself and hands them to AddRowStats);
+  // EvalDone is the bookkeeping behind every evaluated batch.
+  double *DeferredRoom(int32 rows) { return PendingRowStats(rows); }
+  void AddRowStats(const double *rowstats, int32 rows);
+  void EvalDone(int32 rows) { AfterEval(rows); }
 
  private:
   void Fetch();
@@ -123,10 +130,34 @@ class MultiTaskLoss : public LossItf {
   void Eval(const std::vector<BaseFloat> &, const CuMatrixBase &, const CuMatrixBase &, CuMatrix *) { ASLP_ERR << "This is not supposed to be called!"; }
   void Eval(const std::vector<BaseFloat> &frame_weights, const CuMatrixBase &net_out, const Posterior &target, CuMatrix *diff);
   using LossItf::Eval;
+  // Device-resident variant (no host data on the step path).  `loss_input` [rows x sum of the task dims] is the network output or, with
+  // `pre_block_softmax`, the activations in front of a <BlockSoftmax> whose blocks are the tasks (all xent): the kernel then forms the
+  // posteriors and applies the component's backward mask.  labels_dev: [rows x number of xent tasks] in task order, relative to the task's
+  // first column, < 0 = no target.  dense_targets (NULL without an mse task): full width, read in the mse tasks' windows only.
+  // All xent tasks go through one aslp_xent_blocks_eval, their row statistics into each task's own Xent; an mse task through
+  // Mse::EvalInto into its window.  `diff` is the caller's [rows x cols].  With the switch off (Fused()): the op sequence of Eval above --
+  // dense targets scattered from the labels, per task Eval, Scale, CopyFromMat -- and no pre_block_softmax.
+  void EvalDevice(const CuVectorBase &frame_weights, const CuMatrixBase &loss_input, bool pre_block_softmax, const int32 *labels_dev,
+                  const CuMatrixBase *dense_targets, CuMatrixBase *diff);
+  static bool Fused();            // the A/B switch: ASLP_MULTITASK_FUSED=0, or SetFused(false)
+  static void SetFused(bool on);
   std::string Report();
   BaseFloat AvgLoss();
+  // the task table
+  enum TaskKind { kXentTask = 0, kMseTask = 1 };
+  int32 NumTasks() const { return (int32)loss_vec_.size(); }
+  int32 NumXentTasks() const;
+  TaskKind Kind(int32 task) const;
+  int32 Dim(int32 task) const { return loss_dim_[task]; }
+  int32 Offset(int32 task) const { return loss_dim_offset_[task]; }
+  int32 TotalDim() const { return loss_dim_offset_.back(); }
+  BaseFloat Weight(int32 task) const { return loss_weights_[task]; }
+  // a task's raw accumulators: Xent::GetStats' five, or Mse::GetStats' three followed by two zeros
+  void GetTaskStats(int32 task, double out[5]);
 
  private:
+  void EvalTasks(const std::vector<BaseFloat> &frame_weights, const CuMatrixBase &net_out, CuMatrixBase *diff);   // from tgt_mat_
+  CuVectorD rowstats_tmp_;
   std::vector<LossItf *> loss_vec_;
   std::vector<int32> loss_dim_;
   std::vector<BaseFloat> loss_weights_;

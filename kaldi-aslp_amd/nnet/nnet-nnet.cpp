@@ -88,6 +88,8 @@ const CuMatrixBase &Nnet::OutputBuffer(int32 c) const {
   if (FusedSigmoidOf(c) >= 0) ASLP_ERR << "output of component " << c << " is not materialised (fused into the Sigmoid behind it); SetLayerFusion(false)";
   if (softmax_folded_ && (IsFinalSoftmax(c) || c == output_[0]))
     ASLP_ERR << "output of component " << c << " is not materialised (the last step left the final Softmax to the loss kernel); SetLayerFusion(false)";
+  if (block_softmax_folded_ && (IsFinalBlockSoftmax(c) || c == output_[0]))
+    ASLP_ERR << "output of component " << c << " is not materialised (the last step left the final BlockSoftmax to the loss kernel); SetLayerFusion(false)";
   return *out_view_[c];
 }
 const CuMatrixBase &Nnet::OutputDiffBuffer(int32 c) const {
@@ -104,6 +106,7 @@ void Nnet::Propagate(const std::vector<const CuMatrixBase *> &in, std::vector<Cu
   S16EpochScope plane_scope(fwd_epoch_, 0);
   for (size_t i = 0; i < input_.size(); i++) in_view_[input_[i]] = in[i];  // InputLayer reads the caller's matrix
   softmax_folded_ = false;
+  block_softmax_folded_ = false;
   last_fused_activations_ = 0;
   std::vector<char> done(components_.size(), 0);  // Sigmoids already produced by the BatchNormalization in front of them
   for (int32 i = 0; i < (int32)components_.size(); i++) {
@@ -165,6 +168,9 @@ void Nnet::Propagate(const std::vector<const CuMatrixBase *> &in, std::vector<Cu
     } else if (fold_softmax_request_ && IsFinalSoftmax(i)) {
       out_view_[i] = in_view_[i];  // the loss kernel forms the posteriors itself
       softmax_folded_ = true;
+    } else if (fold_block_softmax_request_ && IsFinalBlockSoftmax(i)) {
+      out_view_[i] = in_view_[i];  // ... and the blocks' posteriors (aslp_xent_blocks_eval), with the component's backward mask
+      block_softmax_folded_ = true;
     } else {
       if (components_[i]->GetType() == Component::kInputLayer) {   // the copy of the input also makes the planes the first layer product reads
         const int32 ac = AffineConsumerOf(i);
@@ -184,14 +190,30 @@ void Nnet::Propagate(const std::vector<const CuMatrixBase *> &in, std::vector<Cu
   for (size_t i = 0; i < input_.size(); i++) in_view_[input_[i]] = &output_buf_[input_[i]];
 }
 
-// Softmax whose posteriors are the single network output (directly, or through the auto-added OutputLayer)
-bool Nnet::IsFinalSoftmax(int32 i) const {
-  if (!fuse_layers_ || !alias_links_ || output_.size() != 1 || components_[i]->GetType() != Component::kSoftmax) return false;
-  if (!aslp_softmax_xent_supported(components_[i]->OutputDim())) return false;
+// component of `type` whose output is the single network output (directly, or through the auto-added OutputLayer)
+bool Nnet::IsFinalOutputOfType(int32 i, Component::ComponentType type) const {
+  if (!fuse_layers_ || !alias_links_ || output_.size() != 1 || components_[i]->GetType() != type) return false;
   const int32 o = output_[0];
   if (o == i) return num_consumers_[i] == 0;
   return num_consumers_[i] == 1 && num_consumers_[o] == 0 && components_[o]->GetType() == Component::kOutputLayer && IsDirectLink(o) &&
          components_[o]->GetInput()[0] == i;
+}
+bool Nnet::IsFinalSoftmax(int32 i) const {
+  return IsFinalOutputOfType(i, Component::kSoftmax) && aslp_softmax_xent_supported(components_[i]->OutputDim());
+}
+// ... a BlockSoftmax that reads one producer's whole output, every block within the loss kernel's range
+bool Nnet::IsFinalBlockSoftmax(int32 i) const {
+  if (!IsFinalOutputOfType(i, Component::kBlockSoftmax) || !IsDirectLink(i)) return false;
+  const BlockSoftmax *bs = dynamic_cast<const BlockSoftmax *>(components_[i]);
+  if (bs == NULL || bs->block_dims.empty() || bs->block_dims.size() > 16) return false;
+  for (int32 dim : bs->block_dims)
+    if (!aslp_xent_blocks_supported(dim)) return false;
+  return true;
+}
+const std::vector<int32> *Nnet::FinalBlockSoftmaxDims() const {
+  for (int32 i = 0; i < NumComponents(); i++)
+    if (IsFinalBlockSoftmax(i)) return &dynamic_cast<const BlockSoftmax *>(components_[i])->block_dims;
+  return NULL;
 }
 void Nnet::SetDropoutRetention(BaseFloat r) {  // nnet-nnet.cc:454-464
   for (int32 c = 0; c < NumComponents(); c++) {
@@ -203,12 +225,13 @@ void Nnet::SetDropoutRetention(BaseFloat r) {  // nnet-nnet.cc:454-464
     }
   }
 }
-void Nnet::PropagateForLoss(const CuMatrixBase &in, bool fold_softmax) {
+void Nnet::PropagateForLoss(const CuMatrixBase &in, bool fold_softmax, bool fold_block_softmax) {
   ASLP_ASSERT(input_.size() == 1 && output_.size() == 1);
   std::vector<const CuMatrixBase *> in_vec(1, &in);
   fold_softmax_request_ = fold_softmax;
-  try { Propagate(in_vec, NULL); } catch (...) { fold_softmax_request_ = false; throw; }
-  fold_softmax_request_ = false;
+  fold_block_softmax_request_ = fold_block_softmax;
+  try { Propagate(in_vec, NULL); } catch (...) { fold_softmax_request_ = fold_block_softmax_request_ = false; throw; }
+  fold_softmax_request_ = fold_block_softmax_request_ = false;
 }
 const CuMatrixBase &Nnet::LossInput() const {
   ASLP_ASSERT(output_.size() == 1 && out_view_[output_[0]] != NULL);
@@ -219,14 +242,14 @@ CuMatrix *Nnet::LossDiff(int32 num_frames) {
   CuMatrix *d = &output_diff_buf_[output_[0]];
   d->Resize(num_frames, components_[output_[0]]->OutputDim(), kUndefined);
   // Does this very buffer reach an AffineTransform as its out-diff (through identity backward passes that hand the buffer on:
-  // OutputLayer, the final Softmax)?  Then the loss may leave the diff's fp16 planes with that layer (csrc/split16.h).
+  // OutputLayer, the final Softmax, a BlockSoftmax left to the loss)?  Then the loss may leave the diff's fp16 planes with that layer (csrc/split16.h).
   S16DiffTarget &t = s16_loss_diff_target();
   t = S16DiffTarget();
   next_bwd_epoch_ = 0;
   if (fuse_layers_ && alias_links_) {
     int32 c = output_[0];
     while (c >= 0 && components_[c]->GetType() != Component::kAffineTransform) {
-      const bool hands_on = components_[c]->BackpropIsCopy() && components_[c]->GetType() != Component::kInputLayer && IsDirectLink(c) &&
+      const bool hands_on = HandsLossDiffOn(c) && components_[c]->GetType() != Component::kInputLayer && IsDirectLink(c) &&
                             num_consumers_[components_[c]->GetInput()[0]] == 1;
       c = hands_on ? components_[c]->GetInput()[0] : -1;
     }
@@ -335,7 +358,7 @@ void Nnet::Backpropagate(const std::vector<const CuMatrixBase *> &out_diff, std:
     CuMatrix *target = &input_diff_buf_[i];
     if (!is_input && direct[i]) target = &output_diff_buf_[components_[i]->GetInput()[0]];
     if (!skip_backprop) {
-      if (!is_input && direct[i] && components_[i]->BackpropIsCopy()) {
+      if (!is_input && direct[i] && (components_[i]->BackpropIsCopy() || (diff_in_place_ && HandsLossDiffOn(i)))) {
         // identity backward into the only consumer slot: hand the buffer over instead of copying
         target->Swap(&output_diff_buf_[i]);
         out_diff_view_[i] = target;

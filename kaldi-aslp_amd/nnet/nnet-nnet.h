@@ -101,9 +101,17 @@ class Nnet {
   // network output is read, and the loss's diff is written, in the executor's own buffers, which saves the two
   // full-matrix copies of Propagate(in, &out) / Backpropagate(diff, NULL).  With `fold_softmax` a final Softmax that
   // is the single network output is left to the loss kernel (LossInputIsPreSoftmax() tells whether that happened).
-  void PropagateForLoss(const CuMatrixBase &in, bool fold_softmax);
+  // With `fold_block_softmax` a final <BlockSoftmax> (single network output, every block 1..8192 wide: FinalBlockSoftmaxDims()) is left to
+  // the loss as well: a caller asks for it only when its loss forms the blocks' posteriors AND applies the component's backward mask
+  // (aslp_xent_blocks_eval for MultiTaskLoss tasks that match the blocks), and the executor then hands the loss diff on through the
+  // component as it does through a folded Softmax.
+  void PropagateForLoss(const CuMatrixBase &in, bool fold_softmax, bool fold_block_softmax = false);
   const CuMatrixBase &LossInput() const;
   bool LossInputIsPreSoftmax() const { return softmax_folded_; }
+  bool LossInputIsPreBlockSoftmax() const { return block_softmax_folded_; }
+  int LastLossFold() const { return softmax_folded_ ? 1 : (block_softmax_folded_ ? 2 : 0); }
+  // the block dims of the <BlockSoftmax> a PropagateForLoss(in, *, true) would leave to the loss, or NULL: there is none
+  const std::vector<int32> *FinalBlockSoftmaxDims() const;
   CuMatrix *LossDiff(int32 num_frames);
   void BackpropagateFromLossDiff();
 
@@ -112,6 +120,10 @@ class Nnet {
   void InitInputOutput();
   bool IsDirectLink(int32 i) const;  // single input, offset 0, full width
   bool IsFinalSoftmax(int32 i) const;
+  bool IsFinalOutputOfType(int32 i, Component::ComponentType type) const;   // component i of `type` whose output is the single network output
+  bool IsFinalBlockSoftmax(int32 i) const;
+  // the loss diff passes through component c unchanged: an identity backward pass, or the BlockSoftmax whose mask the loss kernel applied
+  bool HandsLossDiffOn(int32 c) const { return components_[c]->BackpropIsCopy() || (block_softmax_folded_ && IsFinalBlockSoftmax(c)); }
   int32 FusedSigmoidOf(int32 i) const;  // index of the Sigmoid folded into BatchNormalization i, or -1
   int32 BatchNormOf(int32 i) const;      // index of the BatchNormalization that is AffineTransform i's only consumer (direct link), or -1
   int32 AffineSigmoidOf(int32 i) const;   // index of the Sigmoid / Tanh / ReLU whose forward pass rides in AffineTransform i's GEMM, or -1
@@ -132,6 +144,7 @@ class Nnet {
   bool fuse_layers_ = true;
   bool overlap_updates_ = true;
   bool fold_softmax_request_ = false, softmax_folded_ = false, diff_in_place_ = false;
+  bool fold_block_softmax_request_ = false, block_softmax_folded_ = false;
   int32 last_fused_activations_ = 0;
   // weight updates issued on the side stream by the latest Backpropagate and not waited for yet (JoinUpdates(): the main stream waits);
   // the next Propagate joins in front of component first_after_updates_

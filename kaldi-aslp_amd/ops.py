@@ -369,6 +369,39 @@ def mse_eval(net_out, targets, frame_weights, diff, row_loss, scale=1.0, parts=N
     return served, (po.nparts if po is not None else 0)
 
 
+def xent_blocks_eval(inp, blocks, labels, frame_weights, diff, softmax=True, mask=True, post_out=None, parts=None):
+    """aslp_xent_blocks_eval: Xent over column blocks of `inp` in one launch.  blocks: a list of (offset, cols, weight, rowstats) with
+    rowstats a float64 device tensor [rows x 5] (or None, to look at the refusal); labels int32 [rows x len(blocks)], relative to the
+    block, < 0 = no target.  softmax: `inp` holds activations, else posteriors; mask: BlockSoftmax' backward on the diff; post_out
+    (optional) receives the posteriors, parts (256 floats, optional) one maximum of the finite |diff| per workgroup.  Returns
+    (served, nparts); nothing raises, so that a refusal (served == 0, the error string set) can be looked at."""
+    from ._lib import XentBlock
+    for m in (inp, frame_weights, diff, post_out):
+        if m is not None:
+            _chk(m)
+    if labels is not None:
+        _chk(labels, torch.int32)
+    arr = (XentBlock * max(len(blocks), 1))()
+    for k, (offset, cols, weight, rowstats) in enumerate(blocks):
+        arr[k].offset, arr[k].cols, arr[k].weight = int(offset), int(cols), float(weight)
+        arr[k].rowstats = ptr(_chk(rowstats, torch.float64)) if rowstats is not None else None
+    po = None
+    if parts is not None:
+        po = PlanesOut()
+        po.parts = ptr(_chk(parts))
+    d = dim(inp) if inp is not None else MatrixDim(0, 0, 0)
+    served = lib.aslp_xent_blocks_eval(ptr(inp), d, arr, len(blocks), ptr(labels), ptr(frame_weights), ptr(diff),
+                                       dim(diff).stride if diff is not None else 0, int(bool(softmax)), int(bool(mask)), ptr(post_out),
+                                       dim(post_out).stride if post_out is not None else 0, C.byref(po) if po is not None else None)
+    return served, (po.nparts if po is not None else 0)
+
+
+def multitask_fused(on):
+    """A/B switch (ASLP_MULTITASK_FUSED=0): off = nnet.MultiTaskLoss.Eval / Nnet.train_step_multitask run the op sequence of the
+    reference's MultiTaskLoss::Eval, no BlockSoftmax is left to the loss"""
+    lib.aslp_multitask_fused(int(bool(on)))
+
+
 def ctc_loss(acts, labels, input_lengths, want_grad=True):
     """compute_ctc_loss (warp-ctc/include/ctc.h:88-97) on device activations [(maxT*mb) x A] laid out (t, n, p).
     labels: list of int lists; returns (costs numpy[mb], grads tensor or None)."""
