@@ -430,6 +430,20 @@ void aslp_coop_convert(int on);
 int aslp_xent_eval_rows(const float *net_out, MatrixDim d, const int32_cuda *labels, const float *frame_weights, float *diff, int diff_stride,
                         double *rowstats_out, int softmax, const aslp_planes_out *diff_planes);
 void aslp_xent_sum_rowstats(const double *rowstats, int rows, int batches, double *stats_dev);
+/* Xent on soft targets given as they are, sparse: CSR in device memory -- row_begin [d.rows + 1] (row_begin[0] == 0, non-decreasing),
+ * tgt_col [nnz] (strictly increasing within a row), tgt_w [nnz].  An entry whose column is outside [0, d.cols) is skipped and never used
+ * as an address.  One launch over rows of 1 .. 8192 classes (softmax != 0: `in` holds the activations in front of the Softmax, for
+ * aslp_softmax_xent_supported(cols); post_out, nullable, receives the posteriors); diff, posteriors and the five statistics carry the bits
+ * of aslp_xent_eval / aslp_softmax_xent_eval on the dense matrix with m(row, col) = 0.0f + w and zeros elsewhere.  aslp_xent_sparse_eval adds
+ * the statistics to stats_dev (a second launch), aslp_xent_sparse_eval_rows leaves the [d.rows x 5] row statistics to the caller, who adds
+ * them up with aslp_xent_sum_rowstats.  Both return 1, or 0 = refused (a null pointer, a size <= 0, a stride below d.cols, a width
+ * aslp_xent_sparse_supported declines): the error string is set and nothing is launched.  No planes of diff are written. */
+int aslp_xent_sparse_supported(int cols, int softmax);
+int aslp_xent_sparse_eval(const float *in, MatrixDim d, const int32_cuda *row_begin, const int32_cuda *tgt_col, const float *tgt_w,
+                          const float *frame_weights, float *diff, int diff_stride, double *stats_dev, int softmax, float *post_out, int post_stride);
+int aslp_xent_sparse_eval_rows(const float *in, MatrixDim d, const int32_cuda *row_begin, const int32_cuda *tgt_col, const float *tgt_w,
+                               const float *frame_weights, float *diff, int diff_stride, double *rowstats_out, int softmax, float *post_out,
+                               int post_stride);
 /* Mse::Eval (nnet-loss.cc:205-258) in one pass over net_out and tgt [d.rows x d.cols].  Per element in fp32, every operation rounded on
  * its own:  e = (y - t) * w[row];  diff = e, or e * scale as a second rounding when scale != 1 (MultiTaskLoss' Scale);  q = (e * e) * w[row]
  * -- the bits of AddMat(-1), MulRowsVec, MulElements, MulRowsVec.  row_loss[row] (double) = the sum of the row's q in a fixed order, no

@@ -93,6 +93,20 @@ int aslp_xent_get_stats(aslp_xent_t x, double stats[5]);      /* frames, correct
  * (nnet-nnet.cc:70-154 + nnet-loss.cc:63; the loop body of aslp-nnet-train-frame.cc:109-131). */
 int aslp_nnet_train_step_xent(aslp_nnet_t n, aslp_xent_t x, const float *in, int rows, int cols, int stride,
                               const int32_t *labels, const float *frame_weights);
+/* Soft targets (weighted pdfs per frame: pruned teacher posteriors, smoothed alignments, lattice posteriors) as CSR in device memory:
+ * row_begin [rows + 1] (row_begin[0] == 0, non-decreasing), tgt_col [nnz] (strictly increasing within a row; one outside [0, cols) is
+ * skipped), tgt_w [nnz].  One launch over rows of 1 .. 8192 classes, no dense target matrix, nothing read back before report / get_stats;
+ * the bits of aslp_xent_eval_batch on the dense matrix of the same entries.  net_out holds posteriors; frame_weights [rows]; all device. */
+int aslp_xent_eval_sparse_batch(aslp_xent_t x, const float *net_out, int rows, int cols, int stride, const int32_t *row_begin,
+                                const int32_t *tgt_col, const float *tgt_w, int nnz, const float *frame_weights, float *diff, int diff_stride);
+/* aslp_nnet_train_step_xent on such targets: Propagate -> Xent::EvalSparse (in front of a final Softmax where the network leaves it to the
+ * loss) -> Backpropagate.  frame_weights NULL = ones. */
+int aslp_nnet_train_step_xent_sparse(aslp_nnet_t n, aslp_xent_t x, const float *in, int rows, int cols, int stride, const int32_t *row_begin,
+                                     const int32_t *tgt_col, const float *tgt_w, int nnz, const float *frame_weights);
+/* A/B switch (ASLP_XENT_SPARSE=0, read once per process): off = Xent::Eval on a Posterior that is not one-hot builds the dense target matrix
+ * (PosteriorToMatrix) and runs the dense kernel, as before.  The two entry points above are not switched. */
+void aslp_xent_sparse(int on);
+int aslp_xent_sparse_get(void);
 
 /* ---- Mse (nnet-loss.h:120-164) -------------------------------------------------------------- */
 int aslp_mse_create(aslp_mse_t *out);

@@ -269,6 +269,11 @@ _sig("aslp_softmax_xent_supported", _i, _i)
 _sig("aslp_xent_eval_p", _i, _vp, _md, _vp, _vp, _vp, _i, _vp, _i, C.POINTER(PlanesOut))
 _sig("aslp_xent_eval_rows", _i, _vp, _md, _vp, _vp, _vp, _i, _vp, _i, C.POINTER(PlanesOut))
 _sig("aslp_xent_sum_rowstats", None, _vp, _i, _i, _vp)
+_sig("aslp_xent_sparse_supported", _i, _i, _i)
+_sig("aslp_xent_sparse_eval", _i, _vp, _md, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _i)
+_sig("aslp_xent_sparse_eval_rows", _i, _vp, _md, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _i)
+_sig("aslp_xent_sparse", None, _i)
+_sig("aslp_xent_sparse_get", _i)
 _sig("aslp_mse_eval", _i, _vp, _md, _vp, _i, _vp, C.c_float, _vp, _i, _vp, C.POINTER(PlanesOut))
 _sig("aslp_mse_eval_w", _i, _vp, _md, _vp, _i, _vp, C.c_float, _vp, _i, _vp, C.POINTER(PlanesOut), _vp)
 _sig("aslp_mse_batch_sums", None, _vp, _i, _i, _vp)

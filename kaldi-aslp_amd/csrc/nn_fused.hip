@@ -959,10 +959,19 @@ __device__ __forceinline__ void xent_sum_rows(const double *rowstats, int rows, 
 // SOFTMAX: `y` holds the activations in front of the network's final Softmax and the row softmax is formed here,
 // with exactly the arithmetic of softmax_rows_kernel<256> (same lane -> column mapping, same reduction order), so
 // folding the Softmax component into the loss changes no bit; `y_out` (nullable) receives the posteriors.
-template <bool DENSE, bool SOFTMAX, int PER, bool VEC = false>
+// SPARSE (with DENSE): the targets come as CSR -- row r's entries are row_begin[r] .. row_begin[r + 1] - 1 of `labels` (the columns, strictly
+// increasing within a row) and `t` (the weights); an entry whose column is outside [0, cols) is skipped and never used as an address.  The
+// row's entries are laid out in LDS as the dense row they stand for (0.0f + w: what an add onto a zeroed matrix leaves, so -0.0 becomes +0.0),
+// each thread fills its slots from there through its own column map, and everything behind that is the DENSE arithmetic as it stands: the
+// same bits as the dense kernel on the dense matrix.  The lanes that laid an entry out write the zero back once the row has been read, so the
+// staging row is cleared once per workgroup.
+template <bool DENSE, bool SOFTMAX, int PER, bool VEC = false, bool SPARSE = false>
 __global__ void __launch_bounds__(256) xent_rows_kernel(const float *y, int ldy, const float *t, int ldt, const int32_t *labels,
                                                         const float *fw, float *diff, int ldd, int rows, int cols, double *rowstats,
-                                                        float *y_out, int ldyo, S16Out po) {
+                                                        float *y_out, int ldyo, S16Out po, const int32_t *row_begin) {
+  static_assert(!SPARSE || DENSE, "CSR targets are dense targets to the arithmetic");
+  constexpr bool TMAT = DENSE && !SPARSE;   // the targets are read from a matrix
+  __shared__ __attribute__((aligned(16))) float stage[SPARSE ? 256 * PER : 1];
   // VEC: slot k of a thread is column 4 (tid + 256 (k / 4)) + k % 4, every array touched 16 bytes at a time (softmax_rows_kernel's second
   // map, chosen by the same rule: cols % 4 == 0 and 16-byte aligned rows); else column tid + 256 k
   static_assert(!VEC || PER % 4 == 0, "whole groups of four slots");
@@ -972,11 +981,25 @@ __global__ void __launch_bounds__(256) xent_rows_kernel(const float *y, int ldy,
   const float pscale = po.hi ? ldexpf(1.f, s16_exponent(*po.slot)) : 0.f;   // planes of diff for the product that reads it (split16.h)
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   auto col_of = [tid](int k) { return VEC ? 4 * (tid + (k >> 2) * 256) + (k & 3) : tid + k * 256; };
+  if (SPARSE) {
+#pragma unroll
+    for (int k = 0; k < PER; k++) stage[tid + k * 256] = 0.0f;
+    __syncthreads();
+  }
   for (int r = blockIdx.x; r < rows; r += gridDim.x) {
     const float *yr = y + (long)r * ldy;
-    const float *tr = DENSE ? t + (long)r * ldt : nullptr;
+    const float *tr = TMAT ? t + (long)r * ldt : nullptr;
     const int label = DENSE ? -1 : labels[r];
     const float fw_r = fw[r];   // (here, in the row's round trip: read where it is used it is a trip of its own behind the last reduction)
+    // SPARSE: the thread's first entry leaves in front of the row's loads (a row of more than 256 entries takes further rounds below)
+    int e_end = 0, e_next = 0, e_col = -1;
+    float e_w = 0.0f;
+    if (SPARSE) {
+      e_end = row_begin[r + 1];
+      e_next = row_begin[r] + tid;
+      if (e_next < e_end) { e_col = labels[e_next]; e_w = t[e_next]; }
+      e_next += 256;
+    }
     float yv[PER], tv[PER];
     float tsum = 0.0f, ybest = -1e21f, tbest = -1e21f;
     int yi = -1, ti = -1;
@@ -988,7 +1011,7 @@ __global__ void __launch_bounds__(256) xent_rows_kernel(const float *y, int ldy,
         if (c < cols) {
           const float4 v4 = *reinterpret_cast<const float4 *>(yr + c);
           yv[4 * k4] = v4.x; yv[4 * k4 + 1] = v4.y; yv[4 * k4 + 2] = v4.z; yv[4 * k4 + 3] = v4.w;
-          if (DENSE) {
+          if (TMAT) {
             const float4 t4 = *reinterpret_cast<const float4 *>(tr + c);
             tv[4 * k4] = t4.x; tv[4 * k4 + 1] = t4.y; tv[4 * k4 + 2] = t4.z; tv[4 * k4 + 3] = t4.w;
           }
@@ -1000,7 +1023,31 @@ __global__ void __launch_bounds__(256) xent_rows_kernel(const float *y, int ldy,
         const int c = tid + k * 256;
         if (c < cols) {
           yv[k] = yr[c];
-          if (DENSE) tv[k] = tr[c];
+          if (TMAT) tv[k] = tr[c];
+        }
+      }
+    }
+    if (SPARSE) {
+      if (e_col >= 0 && e_col < cols) stage[e_col] = 0.0f + e_w;
+      for (int i = e_next; i < e_end; i += 256) {
+        const int c = labels[i];
+        if (c >= 0 && c < cols) stage[c] = 0.0f + t[i];
+      }
+      __syncthreads();
+      if (VEC) {
+#pragma unroll
+        for (int k4 = 0; k4 < PER / 4; k4++) {
+          const int c = 4 * (tid + k4 * 256);
+          if (c < cols) {
+            const float4 t4 = *reinterpret_cast<const float4 *>(stage + c);
+            tv[4 * k4] = t4.x; tv[4 * k4 + 1] = t4.y; tv[4 * k4 + 2] = t4.z; tv[4 * k4 + 3] = t4.w;
+          }
+        }
+      } else {
+#pragma unroll
+        for (int k = 0; k < PER; k++) {
+          const int c = tid + k * 256;
+          if (c < cols) tv[k] = stage[c];
         }
       }
     }
@@ -1122,6 +1169,13 @@ __global__ void __launch_bounds__(256) xent_rows_kernel(const float *y, int ldy,
     }
     if (lane == 0) { shf[w][0] = tsum; shf[w][1] = ybest; shf[w][2] = tbest; shi[w][0] = yi; shi[w][1] = ti; }
     __syncthreads();
+    if (SPARSE) {   // every thread has read its slots: the staging row back to zeros (the barriers below stand before the next row's entries)
+      if (e_col >= 0 && e_col < cols) stage[e_col] = 0.0f;
+      for (int i = e_next; i < e_end; i += 256) {
+        const int c = labels[i];
+        if (c >= 0 && c < cols) stage[c] = 0.0f;
+      }
+    }
     tsum = shf[0][0] + shf[1][0] + shf[2][0] + shf[3][0];
     ybest = shf[0][1]; yi = shi[0][0]; tbest = shf[0][2]; ti = shi[0][1];
 #pragma unroll
@@ -1836,9 +1890,9 @@ static bool xent_eval_impl(const float *net_out, MatrixDim d, const float *tgt, 
 #define XENT_LAUNCH_P(DENSE, SM, P)                                                                                                       \
   do {                                                                                                                                    \
     if (vec) hipLaunchKernelGGL((xent_rows_kernel<DENSE, SM, P, true>), dim3(g), dim3(256), 0, cur_stream(), net_out, d.stride, tgt, tgt_stride, labels, \
-                                frame_weights, diff, diff_stride, d.rows, d.cols, rowstats, y_out, y_stride, po);                       \
+                                frame_weights, diff, diff_stride, d.rows, d.cols, rowstats, y_out, y_stride, po, nullptr);              \
     else hipLaunchKernelGGL((xent_rows_kernel<DENSE, SM, P>), dim3(g), dim3(256), 0, cur_stream(), net_out, d.stride, tgt, tgt_stride, labels, \
-                            frame_weights, diff, diff_stride, d.rows, d.cols, rowstats, y_out, y_stride, po);                           \
+                            frame_weights, diff, diff_stride, d.rows, d.cols, rowstats, y_out, y_stride, po, nullptr);                  \
   } while (0)
 #define XENT_LAUNCH(DENSE, SM)                                        \
   do {                                                                \
@@ -1899,6 +1953,62 @@ void aslp_softmax_xent_eval(const float *acts, MatrixDim d, const float *tgt, in
                             const float *frame_weights, float *diff, int diff_stride, double *stats_dev, float *post_out, int post_stride) {
   if (!aslp_softmax_xent_supported(d.cols)) { set_error("aslp_softmax_xent_eval: unsupported number of classes"); return; }
   xent_eval_impl(acts, d, tgt, tgt_stride, labels, frame_weights, diff, diff_stride, stats_dev, true, post_out, post_stride);
+}
+
+// Xent on CSR targets (xent_rows_kernel<true, *, *, *, true>): the rung and the access path are chosen as xent_eval_impl chooses them for the
+// dense matrix the entries stand for -- minus the target matrix' alignment, there being none.  false = refused, nothing launched.
+int aslp_xent_sparse_supported(int cols, int softmax) {
+  return softmax ? aslp_softmax_xent_supported(cols) : (cols >= 1 && cols <= 256 * kXentPerThread ? 1 : 0);
+}
+static bool xent_sparse_impl(const char *who, const float *in, MatrixDim d, const int32_cuda *row_begin, const int32_cuda *tgt_col, const float *tgt_w,
+                             const float *frame_weights, float *diff, int diff_stride, double *stats_dev, double *rowstats_out, bool softmax,
+                             float *y_out, int y_stride) {
+  auto refuse = [&](const char *what) { set_error(std::string(who) + ": " + what); return false; };
+  if (!in || !row_begin || !tgt_col || !tgt_w || !frame_weights || !diff || (!stats_dev && !rowstats_out)) return refuse("null argument");
+  if (d.rows <= 0 || d.cols <= 0 || d.stride < d.cols || diff_stride < d.cols || (y_out && y_stride < d.cols))
+    return refuse("sizes must be positive and no stride smaller than the number of columns");
+  if (!aslp_xent_sparse_supported(d.cols, softmax ? 1 : 0)) return refuse("unsupported number of classes");
+  if (!softmax) y_out = nullptr;   // (the posteriors are the input)
+  double *rowstats = rowstats_out ? rowstats_out : static_cast<double *>(scratch(kScratchReduce, sizeof(double) * 5 * (size_t)d.rows));
+  if (!rowstats) return false;
+  const int g = d.rows > kMaxGrid * 2 ? kMaxGrid * 2 : d.rows;
+  const int per = (d.cols + 255) / 256;
+  const S16Out po = {nullptr, nullptr, 0, nullptr, nullptr};
+  const bool vec = softmax_rows_vec_ok(d.cols) && (d.stride & 3) == 0 && aligned16(in) && (diff_stride & 3) == 0 && aligned16(diff) &&
+                   (!y_out || ((y_stride & 3) == 0 && aligned16(y_out)));
+#define XENT_SPARSE_P(SM, P)                                                                                                                      \
+  do {                                                                                                                                            \
+    if (vec) hipLaunchKernelGGL((xent_rows_kernel<true, SM, P, true, true>), dim3(g), dim3(256), 0, cur_stream(), in, d.stride, tgt_w, 0, tgt_col, \
+                                frame_weights, diff, diff_stride, d.rows, d.cols, rowstats, y_out, y_stride, po, row_begin);                      \
+    else hipLaunchKernelGGL((xent_rows_kernel<true, SM, P, false, true>), dim3(g), dim3(256), 0, cur_stream(), in, d.stride, tgt_w, 0, tgt_col,   \
+                            frame_weights, diff, diff_stride, d.rows, d.cols, rowstats, y_out, y_stride, po, row_begin);                          \
+  } while (0)
+#define XENT_SPARSE(SM)                                \
+  do {                                                 \
+    if (per <= 4) XENT_SPARSE_P(SM, 4);                \
+    else if (per <= 8) XENT_SPARSE_P(SM, 8);           \
+    else if (per <= 16) XENT_SPARSE_P(SM, 16);         \
+    else XENT_SPARSE_P(SM, 32);                        \
+  } while (0)
+  if (softmax) XENT_SPARSE(true); else XENT_SPARSE(false);
+#undef XENT_SPARSE
+#undef XENT_SPARSE_P
+  if (!rowstats_out) hipLaunchKernelGGL(xent_finalize_kernel, dim3(1), dim3(256), 0, cur_stream(), rowstats, d.rows, stats_dev);
+  check_launch(who);
+  return true;
+}
+int aslp_xent_sparse_eval(const float *in, MatrixDim d, const int32_cuda *row_begin, const int32_cuda *tgt_col, const float *tgt_w,
+                          const float *frame_weights, float *diff, int diff_stride, double *stats_dev, int softmax, float *post_out, int post_stride) {
+  if (!stats_dev) { set_error("aslp_xent_sparse_eval: null argument"); return 0; }
+  return xent_sparse_impl("aslp_xent_sparse_eval", in, d, row_begin, tgt_col, tgt_w, frame_weights, diff, diff_stride, stats_dev, nullptr, softmax != 0,
+                          post_out, post_stride) ? 1 : 0;
+}
+int aslp_xent_sparse_eval_rows(const float *in, MatrixDim d, const int32_cuda *row_begin, const int32_cuda *tgt_col, const float *tgt_w,
+                               const float *frame_weights, float *diff, int diff_stride, double *rowstats_out, int softmax, float *post_out,
+                               int post_stride) {
+  if (!rowstats_out) { set_error("aslp_xent_sparse_eval_rows: no room for the per-row statistics"); return 0; }
+  return xent_sparse_impl("aslp_xent_sparse_eval_rows", in, d, row_begin, tgt_col, tgt_w, frame_weights, diff, diff_stride, nullptr, rowstats_out,
+                          softmax != 0, post_out, post_stride) ? 1 : 0;
 }
 
 // Mse::Eval in one launch (mse_rows_kernel above).  16-byte accesses where all three matrices allow them, one column per access elsewhere

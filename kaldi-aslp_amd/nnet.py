@@ -52,6 +52,8 @@ _sig("aslp_xent_eval_batch", _i, _H, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _i
 _sig("aslp_xent_report", _i, _H, C.c_char_p, _i)
 _sig("aslp_xent_get_stats", _i, _H, C.POINTER(C.c_double))
 _sig("aslp_nnet_train_step_xent", _i, _H, _H, _vp, _i, _i, _i, _vp, _vp)
+_sig("aslp_xent_eval_sparse_batch", _i, _H, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _i)
+_sig("aslp_nnet_train_step_xent_sparse", _i, _H, _H, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _vp)
 _sig("aslp_mse_create", _i, C.POINTER(_H))
 _sig("aslp_mse_free", None, _H)
 _sig("aslp_mse_eval_batch", _i, _H, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _i)
@@ -83,6 +85,36 @@ def _ok(rc):
     check_error()
 
 
+def posterior_to_csr(post, num_cols, device):
+    """A posterior -- per frame a list of (pdf, weight) pairs -- as the CSR tensors (row_begin int32 [frames + 1], cols int32 [nnz],
+    weights float32 [nnz]) that Xent.EvalSparse and Nnet.train_step_xent_sparse take, under the rules of the engine's PosteriorToMatrix:
+    a later duplicate of a pdf wins, a pdf >= num_cols is an error, a negative one is dropped, the pdfs sorted within the frame."""
+    row_begin, cols, weights = [0], [], []
+    for frame in post:
+        last = {}
+        for pdf, w in frame:
+            pdf = int(pdf)
+            if pdf >= num_cols:
+                raise ValueError("Out-of-bound Posterior element with index %d, higher than number of columns %d" % (pdf, num_cols))
+            if pdf >= 0:
+                last[pdf] = float(w)
+        for pdf in sorted(last):
+            cols.append(pdf)
+            weights.append(last[pdf])
+        row_begin.append(len(cols))
+    # (an empty posterior still gets one element to point at: the entry points take no null pointer)
+    return (torch.tensor(row_begin, dtype=torch.int32, device=device), torch.tensor(cols or [0], dtype=torch.int32, device=device)[:len(cols) or 1],
+            torch.tensor(weights or [0.0], dtype=torch.float32, device=device)[:len(cols) or 1])
+
+
+def _chk_csr(rows, row_begin, cols, weights):
+    _chk(row_begin, torch.int32), _chk(cols, torch.int32), _chk(weights)
+    if row_begin.numel() != rows + 1:
+        raise ValueError("row_begin must hold rows + 1 offsets")
+    if cols.numel() != weights.numel():
+        raise ValueError("cols and weights must have one length")
+
+
 class Xent:
     def __init__(self):
         self.h = _H()
@@ -98,6 +130,16 @@ class Xent:
         _ok(lib.aslp_xent_eval_batch(self.h, ptr(net_out), net_out.shape[0], net_out.shape[1], dim(net_out).stride,
                                      ptr(targets), dim(targets).stride if targets is not None else 0, ptr(labels),
                                      ptr(frame_weights), ptr(diff), dim(diff).stride))
+
+    def EvalSparse(self, frame_weights, net_out, diff, row_begin, cols, weights):
+        """Eval on soft targets given as CSR device tensors (posterior_to_csr): one launch, no dense target matrix, the bits of
+        Eval(targets=<the dense matrix of the same entries>); net_out holds posteriors of 1 .. 8192 classes"""
+        _chk(net_out), _chk(diff), _chk(frame_weights)
+        _chk_csr(net_out.shape[0], row_begin, cols, weights)
+        if diff.shape != net_out.shape:
+            raise ValueError("net_out and diff must have one shape")
+        _ok(lib.aslp_xent_eval_sparse_batch(self.h, ptr(net_out), net_out.shape[0], net_out.shape[1], dim(net_out).stride, ptr(row_begin),
+                                            ptr(cols), ptr(weights), cols.numel(), ptr(frame_weights), ptr(diff), dim(diff).stride))
 
     def Report(self):
         buf = C.create_string_buffer(4096)
@@ -596,6 +638,16 @@ class Nnet:
             raise ValueError("targets must be [rows x OutputDim()]")
         _ok(lib.aslp_nnet_train_step_multitask(self.h, loss.h, ptr(x), x.shape[0], x.shape[1], dim(x).stride, ptr(labels), ptr(targets),
                                                dim(targets).stride if targets is not None else 0, ptr(frame_weights)))
+
+    def train_step_xent_sparse(self, xent, x, row_begin, cols, weights, frame_weights=None):
+        """Propagate -> Xent::EvalSparse -> Backpropagate(+Update), all on the device, on soft targets given as CSR device tensors
+        (posterior_to_csr); frame_weights [rows] or None.  A final Softmax of 513 .. 8192 classes is left to the loss kernel."""
+        _chk(x)
+        _chk_csr(x.shape[0], row_begin, cols, weights)
+        if frame_weights is not None:
+            _chk(frame_weights)
+        _ok(lib.aslp_nnet_train_step_xent_sparse(self.h, xent.h, ptr(x), x.shape[0], x.shape[1], dim(x).stride, ptr(row_begin), ptr(cols),
+                                                 ptr(weights), cols.numel(), ptr(frame_weights)))
 
     def LastLossFold(self):
         """what the latest train step left to its loss kernel: 0 nothing, 1 the final Softmax, 2 the final BlockSoftmax"""

@@ -272,6 +272,35 @@ int aslp_nnet_train_step_xent(aslp_nnet_t n, aslp_xent_t x, const float *in, int
   API_END
 }
 
+void aslp_xent_sparse(int on) { Xent::SetSparse(on != 0); }
+int aslp_xent_sparse_get(void) { return Xent::Sparse() ? 1 : 0; }
+int aslp_xent_eval_sparse_batch(aslp_xent_t x, const float *net_out, int rows, int cols, int stride, const int32_t *row_begin,
+                                const int32_t *tgt_col, const float *tgt_w, int nnz, const float *frame_weights, float *diff, int diff_stride) {
+  API_BEGIN
+  if (!x || !net_out || !row_begin || !tgt_col || !tgt_w || !frame_weights || !diff || rows <= 0 || cols <= 0 || nnz < 0)
+    ASLP_ERR << "aslp_xent_eval_sparse_batch: null argument or empty matrix";
+  // straight onto the kernel, into the caller's diff; the row statistics stay parked inside x
+  CuSubMatrix y(const_cast<float *>(net_out), rows, cols, stride), d(diff, rows, cols, diff_stride);
+  CuSubVector fwv(const_cast<float *>(frame_weights), rows);
+  x->xent.EvalSparseInto(fwv, y, false, row_begin, tgt_col, tgt_w, &d);
+  API_END
+}
+int aslp_nnet_train_step_xent_sparse(aslp_nnet_t n, aslp_xent_t x, const float *in, int rows, int cols, int stride, const int32_t *row_begin,
+                                     const int32_t *tgt_col, const float *tgt_w, int nnz, const float *frame_weights) {
+  API_BEGIN
+  if (!n || !x || !in || !row_begin || !tgt_col || !tgt_w || nnz < 0) ASLP_ERR << "aslp_nnet_train_step_xent_sparse: null argument";
+  CuSubMatrix inm(const_cast<float *>(in), rows, cols, stride);
+  n->nnet.PropagateForLoss(inm, true);
+  if (frame_weights == NULL) {
+    if (n->fw.Dim() != rows) { n->fw.Resize(rows, kUndefined); n->fw.Set(1.0f); }
+    frame_weights = n->fw.Data();
+  }
+  CuSubVector fwv(const_cast<float *>(frame_weights), rows);
+  x->xent.EvalSparse(fwv, n->nnet.LossInput(), n->nnet.LossInputIsPreSoftmax(), row_begin, tgt_col, tgt_w, n->nnet.LossDiff(rows));
+  n->nnet.BackpropagateFromLossDiff();
+  API_END
+}
+
 int aslp_mse_create(aslp_mse_t *out) { API_BEGIN *out = new aslp_mse_s(); API_END }
 void aslp_mse_free(aslp_mse_t m) { delete m; }
 int aslp_mse_eval_batch(aslp_mse_t m, const float *net_out, int rows, int cols, int stride, const float *targets, int tgt_stride,

@@ -51,6 +51,18 @@ class Xent : public LossItf {
   // `loss_input` is the network output, or the activations in front of its final Softmax when `pre_softmax`
   void EvalOnLossInput(const std::vector<BaseFloat> &frame_weights, const CuMatrixBase &loss_input, bool pre_softmax, const Posterior &target,
                        CuMatrix *diff);
+  // Soft targets as the sparse object they are: CSR in device memory (row_begin [rows + 1], columns strictly increasing within a row,
+  // weights; include/aslp_kernels.h: aslp_xent_sparse_eval).  One launch, the row statistics deferred as on the label path; the bits of
+  // Eval(frame_weights, net_out, <dense matrix of the same entries>, diff).  `loss_input` as for EvalOnLossInput.
+  void EvalSparse(const CuVectorBase &frame_weights, const CuMatrixBase &loss_input, bool pre_softmax, const int32 *row_begin_dev,
+                  const int32 *col_dev, const float *w_dev, CuMatrix *diff);
+  // ... into a matrix the caller owns (not resized: a C ABI caller's buffer)
+  void EvalSparseInto(const CuVectorBase &frame_weights, const CuMatrixBase &loss_input, bool pre_softmax, const int32 *row_begin_dev,
+                      const int32 *col_dev, const float *w_dev, CuMatrixBase *diff);
+  // The A/B switch of the Posterior route (ASLP_XENT_SPARSE=0, read once per process; aslp_xent_sparse): off = PosteriorToMatrix and the
+  // dense kernel, as before.  EvalSparse itself is not switched.
+  static bool Sparse();
+  static void SetSparse(bool on);
   std::string Report();
   BaseFloat AvgLoss() { Fetch(); return (loss_ - entropy_) / frames_; }
   // raw accumulators {frames, correct, loss, entropy, likelyhood}
@@ -72,6 +84,11 @@ class Xent : public LossItf {
   CuVector frame_weights_;
   CuMatrix tgt_mat_;
   CuArray<int32> labels_;
+  // a non-one-hot Posterior as CSR under PosteriorToMatrix' rules, in one buffer {row_begin [rows + 1], columns [nnz], weights' bits [nnz]}:
+  // built in csr_host_, sent with one copy into csr_ (both grow, neither shrinks).  frame_weights_ holds the batch's weights.
+  void EvalPosteriorSparse(const CuMatrixBase &loss_input, bool pre_softmax, const Posterior &post, CuMatrix *diff);
+  std::vector<int32> csr_host_;
+  CuArray<int32> csr_;
   CuVectorD stats_;  // device accumulators
   bool dirty_;
   // The label-target evaluations (the step path) leave their per-row statistics here, batch after batch, and the sum into stats_ is made

@@ -346,6 +346,50 @@ def xent_sum_rowstats(rowstats, rows, batches, stats):
     check_error()
 
 
+def _xent_sparse(fn, inp, row_begin, cols, weights, frame_weights, diff, out, softmax, post_out):
+    for m in (inp, weights, frame_weights, diff, post_out):
+        if m is not None:
+            _chk(m)
+    for m in (row_begin, cols):
+        if m is not None:
+            _chk(m, torch.int32)
+    if out is not None:
+        _chk(out, torch.float64)
+    d = dim(inp) if inp is not None else MatrixDim(0, 0, 0)
+    return fn(ptr(inp), d, ptr(row_begin), ptr(cols), ptr(weights), ptr(frame_weights), ptr(diff), dim(diff).stride if diff is not None else 0,
+              ptr(out), int(bool(softmax)), ptr(post_out), dim(post_out).stride if post_out is not None else 0)
+
+
+def xent_sparse_eval(inp, row_begin, cols, weights, frame_weights, diff, stats, softmax=False, post_out=None):
+    """aslp_xent_sparse_eval: Xent on soft targets given as CSR (row_begin int32 [rows + 1], cols int32 [nnz] strictly increasing within a
+    row, weights [nnz]) in one launch, the five sums added to stats (float64 [5]).  softmax: `inp` holds the activations in front of the
+    Softmax and post_out (optional) receives the posteriors.  Returns served; nothing raises, so that a refusal (served == 0, the error
+    string set) can be looked at: the caller reads last_error() / check_error()."""
+    return _xent_sparse(lib.aslp_xent_sparse_eval, inp, row_begin, cols, weights, frame_weights, diff, stats, softmax, post_out)
+
+
+def xent_sparse_eval_rows(inp, row_begin, cols, weights, frame_weights, diff, rowstats, softmax=False, post_out=None):
+    """aslp_xent_sparse_eval_rows: the same, the batch's per-row statistics left in rowstats (float64 [rows x 5]) for xent_sum_rowstats"""
+    return _xent_sparse(lib.aslp_xent_sparse_eval_rows, inp, row_begin, cols, weights, frame_weights, diff, rowstats, softmax, post_out)
+
+
+def set_xent_sparse(on):
+    """A/B switch (ASLP_XENT_SPARSE=0): off = the engine's Xent::Eval on a Posterior that is not one-hot builds the dense target matrix and
+    runs the dense kernel, as before; on (the default) = the posterior goes to the kernel as CSR.  Same bits either way."""
+    lib.aslp_xent_sparse(int(bool(on)))
+
+
+@contextlib.contextmanager
+def xent_sparse(on):
+    """the engine's evaluations inside the block run with the switch at `on`; the setting in force before comes back on exit"""
+    before = lib.aslp_xent_sparse_get()
+    lib.aslp_xent_sparse(int(bool(on)))
+    try:
+        yield
+    finally:
+        lib.aslp_xent_sparse(before)
+
+
 def mse_eval(net_out, targets, frame_weights, diff, row_loss, scale=1.0, parts=None, frames_out=None):
     """aslp_mse_eval: diff = (net_out - targets) * w[row] (* scale), row_loss[row] (float64) = the row's sum of (e * e) * w[row]; parts
     (256 floats, optional) receives one maximum of the finite |diff| per workgroup.  Returns (served, nparts); nothing raises, so that a
